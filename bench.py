@@ -17,7 +17,13 @@ N > 1: `python bench.py --gpus N` re-executes itself under torch.distributed.run
 own torchrun launch is used as is.  Batch sharding (weak scaling, 64 images per GPU), one RCCL all-gather of the
 token ids per step (event-timed, reported), every rank decodes its slice of the GATHERED id matrix.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the --steps steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config, the analytic job_roofline).  --dump-outputs DIR also writes what the last timed step returned to its
+caller: DIR/images.npy (float32 [B,3,256,256], rank 0's decoded images) and DIR/tokens.npy (float32 [world*B,K], the gathered
+ids), at most 64 MB together (a seeded sample of the image rows beyond that, their indices in DIR/images_index.npy).
+
+--full adds every other leg below (the default line before --full existed); --latency adds the B = 1 leg either way.
+Extra objects on the JSON line with --full:
   roofline          : the VQ nearest-code kernel (vq_f16_kernel, the dominant launch of the VQ path), timed live with HIP events on
                       its launch stream inside the timed steps: frac = EXECUTED f16-MFMA FLOPs / kernel time / the f16 matrix peak.
   roofline_kernels  : the other kernels a step is made of (attention, LN+modulate, fp32 GEMM, f16x2-split GEMM), event-timed
@@ -83,7 +89,36 @@ def parse(argv=None):
                     "(communicator bound to the GPU, int32 cast, side stream, event join) exactly as an N-rank run does -- the 8-GPU line minus the xGMI transport")
     ap.add_argument("--selftest-dist", action="store_true",
                     help="no GPU work: initialise the ranks, all-gather synthetic ids, print the JSON skeleton (CPU test of the N>1 entry)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (other GEMM arithmetic, exact step, VQ and kernel rooflines, "
+                    "token / parity checks against the oracle and the reference goldens, CPU baseline); the --no-* options switch single legs off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned (images, gathered ids) "
+                    "as DIR/<name>.npy in float32, at most 64 MB in all.  Inputs are the same in every run with the same arguments; with --tune-gemm 1 "
+                    "the fp32 Linears run the hipBLASLt kernels a timing picked, so the images of two processes may differ slightly (--tune-gemm 0: bit-equal)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, images, ids, budget=DUMP_BUDGET_BYTES, seed=0x5E1F):
+    """the last timed step's results as float32 .npy files: ids are < 2^24 (exact in float32), the bf16 pixels widen exactly.  Image rows
+    beyond the byte budget are replaced by a fixed seeded sample of rows (same arguments -> same rows), listed in images_index.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    ids = ids.detach().to("cpu", torch.float32).numpy()
+    imgs = images.detach().to("cpu", torch.float32).numpy()
+    written = {"tokens": ids}
+    per_row = imgs[0].nbytes if len(imgs) else 1
+    keep = max(0, (budget - ids.nbytes - 8 * len(imgs)) // per_row)
+    if keep < len(imgs):
+        idx = np.sort(np.random.default_rng(seed).choice(len(imgs), size=keep, replace=False))
+        imgs = imgs[idx]
+        written["images_index"] = idx.astype(np.float64)
+    written["images"] = imgs
+    for name, arr in written.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr))
+    return {name: list(arr.shape) for name, arr in written.items()}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -724,6 +759,9 @@ def main(argv=None):
     vsd = W.synthetic_vae_state_dict(device=dev)
     pipe = SelftokPipeline(cfg, None, None, device=dev, state_dict=sd, vae_state_dict=vsd, verbose=False, gemm=args.gemm, vae_mode=args.vae,
                            tune_gemm=bool(args.tune_gemm), encoder_mode=args.encoder, vae_decode_mode=args.vae_decode)
+    if not args.full:                                  # a plain run: the headline figure only
+        args.no_other_gemm = args.no_kernel_roofs = args.no_parity16 = args.no_parity64 = True
+        args.no_token_check = args.no_cpu_baseline = args.no_exact = True
     if world > 1 and not args.all_legs:                # the N > 1 line = the timed steps + the cheap checks; the deep dives belong to the N = 1 line
         args.no_other_gemm = args.no_kernel_roofs = args.no_parity16 = args.no_parity64 = True
         args.latency = False
@@ -749,16 +787,19 @@ def main(argv=None):
         else:
             out = pipe.decoding(mine, max_steps=args.decode_steps)   # noise: torch.randn on the CPU generator, as the reference
         last["ids_all"] = gather.wait()                           # the API result [world*B, K]: joined on the device, behind the decode
+        last["out"] = out if args.dump_outputs else None
         ag["ms"].append(gather.last_ms())
         return out
 
-    def timed(nsteps, nwarm):
+    def timed(nsteps, nwarm, events=False):
         torch.manual_seed(1234 + rank)
+        t_w = time.perf_counter()
         for _ in range(nwarm):
             step()
-        ops.VQ_EVENTS = []
+        ops.VQ_EVENTS = [] if events else None    # HIP events around the VQ launches: only the roofline object of --full reads them
         ag["ms"].clear()
         torch.cuda.synchronize()
+        last["warmup_s"] = time.perf_counter() - t_w
         D.barrier()
         t0 = time.perf_counter()
         for _ in range(nsteps):
@@ -769,7 +810,13 @@ def main(argv=None):
         ev, ops.VQ_EVENTS = ops.VQ_EVENTS, None
         return el, ev
 
-    elapsed, vq_events = timed(args.steps, args.warmup)
+    setup_s = time.perf_counter() - T_PROCESS_START
+    elapsed, vq_events = timed(args.steps, args.warmup, events=args.full)
+    warmup_s = last["warmup_s"]
+    dumped = None
+    if args.dump_outputs and rank == 0:                 # before any other leg runs a step: the last TIMED step's results
+        dumped = dump_outputs(args.dump_outputs, last["out"], last["ids_all"])
+    last["out"] = None
 
     # ---- the same step on the other GEMM arithmetic (all ranks take part: barriers inside) ----
     other = None
@@ -799,15 +846,17 @@ def main(argv=None):
     if rank != 0:
         D.shutdown()
         return
-    n_vq = B * K
-    vq_main = float(np.mean([a.elapsed_time(b) for a, b, _ in vq_events])) if vq_events else float("nan")
-    vq_fin = float(np.mean([b.elapsed_time(c) for _, b, c in vq_events])) if vq_events else float("nan")
-    # the fp32-input MFMA kernel of round 1 on the same features, for reference (same ids, bit for bit)
-    zf = pipe.model.encoder.features(pipe.encode_latents(images))
-    _, lm, lf = ops.vq_encode_split_launch(zf, pipe.model.encoder.codebook_packed, coarse=False)
-    fp32_main, fp32_fin = event_time_ms(lm, n=20), event_time_ms(lf, n=20)
-    traffic, traffic_note = measured_vq_traffic(n_vq, ops.VQ_DEFAULT_COARSE)
-    roof = vq_roofline(n_vq, 32768, 16, vq_main, vq_fin, len(vq_events), traffic, traffic_note, fp32_main, fp32_fin, mfmas=ops.VQ_COARSE_MFMAS)
+    roof = None
+    if args.full:
+        n_vq = B * K
+        vq_main = float(np.mean([a.elapsed_time(b) for a, b, _ in vq_events])) if vq_events else float("nan")
+        vq_fin = float(np.mean([b.elapsed_time(c) for _, b, c in vq_events])) if vq_events else float("nan")
+        # the fp32-input MFMA kernel of round 1 on the same features, for reference (same ids, bit for bit)
+        zf = pipe.model.encoder.features(pipe.encode_latents(images))
+        _, lm, lf = ops.vq_encode_split_launch(zf, pipe.model.encoder.codebook_packed, coarse=False)
+        fp32_main, fp32_fin = event_time_ms(lm, n=20), event_time_ms(lf, n=20)
+        traffic, traffic_note = measured_vq_traffic(n_vq, ops.VQ_DEFAULT_COARSE)
+        roof = vq_roofline(n_vq, 32768, 16, vq_main, vq_fin, len(vq_events), traffic, traffic_note, fp32_main, fp32_fin, mfmas=ops.VQ_COARSE_MFMAS)
     arith = {"fp32": "fp32 Q-Former/VQ/MMDiT (hipBLASLt fp32 GEMMs), bf16 SD3-VAE (reference dtypes)",
              "exact": "every operation of Q-Former, VQ, MMDiT and VAE as the sequence of fp32 / bf16 operations the reference's torch-CPU run executes (MKL / oneDNN / ATen / Sleef orders "
                       "on chained fp32 MFMAs): ids, latents and pixels bit-equal to the reference's",
@@ -834,8 +883,11 @@ def main(argv=None):
                    "weights": "hash-generated, architecture of tokenizer_512_ckpt"},
         "ranks": world, "backend": backend if (world > 1 or args.force_collective) else None,
         "allgather_bytes": ag["bytes"], "allgather_ms": round(float(np.mean(ag["ms"])), 4) if (world > 1 or args.force_collective) and ag["ms"] else None,
-        "roofline": roof,
     }
+    if roof is not None:
+        line["roofline"] = roof
+    if dumped is not None:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "dtype": "float32", "of": "the last timed step (rank 0)"}
     fl_img = fp32_flops_per_image(K, pipe.k_table[: (args.decode_steps or 50)], renderer)
     job_tf = fl_img * world * B * args.steps / elapsed / 1e12
     line["job_roofline"] = {"bound": "mfma", "unit": "TFLOP/s", "fp32_tflop_per_image": round(fl_img / 1e12, 2),
@@ -858,7 +910,8 @@ def main(argv=None):
                         "-- final latents and pixels bit-equal to the reference pipeline's (parity_16.exact_mode, parity_64.exact)")
     if args.decode_steps is not None and not renderer:
         line["config"]["INVALID"] = "decode loop truncated with --decode-steps (debug run)"
-    legs = {"timed_region": round(elapsed * (args.steps + args.warmup) / max(args.steps, 1), 1),
+    legs = {"setup": round(setup_s, 1), "warmup_steps": round(warmup_s, 1), "timed_steps": round(elapsed, 1),
+            "timed_region": round(elapsed * (args.steps + args.warmup) / max(args.steps, 1), 1),
             "other_gemm_steps": round(other["ms_per_step"] * (other["steps"] + other["warmup"]) / 1e3, 1) if other else 0.0}        # seconds each part of this run took (the run's own wall clock, rank 0)
 
     def leg(name, fn):

@@ -399,6 +399,32 @@ def test_default_config_equals_the_reference_yamls():
     assert gold["k512"]["tokenizer"]["params"]["decoder_config"]["time_adaln"] == "pos_emb" and gold["k512"]["tokenizer"]["params"]["k"] == 512
 
 
+def test_bench_plain_run_is_lean_and_dumps_within_budget(tmp_path):
+    """a plain `bench.py --gpus 1 --steps N --warmup W` times the headline only (the other legs need --full); --dump-outputs writes the last
+    step's results as float32 .npy, exactly for what fits, a seeded row sample of the images beyond the byte budget (the same rows every run)"""
+    import numpy as np
+    m = _bench_module()
+    a = m.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.steps == 3 and a.warmup == 1 and not a.full and a.dump_outputs is None
+    a = m.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    ids = torch.randint(0, 32768, (4, 512), dtype=torch.int64)
+    imgs = torch.rand(4, 3, 8, 8).to(torch.bfloat16)
+    got = m.dump_outputs(str(tmp_path / "all"), imgs, ids)
+    assert got == {"tokens": [4, 512], "images": [4, 3, 8, 8]}
+    t, im = np.load(tmp_path / "all" / "tokens.npy"), np.load(tmp_path / "all" / "images.npy")
+    assert t.dtype == np.float32 and np.array_equal(t.astype(np.int64), ids.numpy())
+    assert im.dtype == np.float32 and np.array_equal(im, imgs.float().numpy())
+    budget = ids.numel() * 4 + 32 + 2 * imgs[0].numel() * 4            # room for the ids and two image rows
+    for d in ("s1", "s2"):
+        got = m.dump_outputs(str(tmp_path / d), imgs, ids, budget=budget)
+        assert got["images"] == [2, 3, 8, 8] and got["images_index"] == [2]
+    i1, i2 = np.load(tmp_path / "s1" / "images_index.npy"), np.load(tmp_path / "s2" / "images_index.npy")
+    assert np.array_equal(i1, i2) and i1.dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "s1" / "images.npy"), imgs.float().numpy()[i1.astype(np.int64)])
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= budget + 3 * 128   # + the .npy headers
+
+
 def test_driver_scripts_have_no_undefined_names():
     """bench.py cannot run without a GPU, so a misspelt or misplaced global would only show at the round-end run (it did once, round 6): every name the driver's
     entry scripts and the package modules LOAD must be bound somewhere in the same file (imports, definitions, assignments, arguments) or be a builtin"""

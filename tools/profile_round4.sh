@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:?}
 O=$R/gpurun_out/prof_r4
 mkdir -p "$O"
-COMMON="--steps 1 --warmup 1 --no-cpu-baseline --no-token-check --no-kernel-roofs --no-other-gemm --no-latency"
+COMMON="--full --steps 1 --warmup 1 --no-cpu-baseline --no-token-check --no-kernel-roofs --no-other-gemm --no-latency"
 for mode in fp32 f16x2; do
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/$mode" -o bench -- python "$R/bench.py" $COMMON --gemm $mode > "$O/bench_$mode.log" 2>&1
   grep -o '{"metric.*' "$O/bench_$mode.log" > "$O/r4_bench_${mode}_under_rocprof.json"
@@ -18,7 +18,7 @@ done
 bash "$R/tools/pmc_vq_traffic.sh" > "$O/pmc_vq_traffic.log" 2>&1
 cp "$R/gpurun_out/pmc_vq/vq_traffic.json" "$O/vq_traffic.json"
 SELFTOK_ONE_GPU=1 SELFTOK_DIST_BACKEND=gloo timeout 600 python "$R/bench.py" --gpus 2 --batch 8 $COMMON 2> "$O/dryrun2.err" | grep -o '{"metric.*' > "$O/r4_bench_dryrun_2ranks_gloo_one_gpu.json"
-timeout 900 python "$R/bench.py" --tokens 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-token-check --no-kernel-roofs --no-latency 2>/dev/null | grep -o '{"metric.*' > "$O/r4_bench_config2_k1024.json"
+timeout 900 python "$R/bench.py" --full --tokens 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-token-check --no-kernel-roofs --no-latency 2>/dev/null | grep -o '{"metric.*' > "$O/r4_bench_config2_k1024.json"
 # where the waves of the two new hot kernels spend their cycles (SQ counters, one PMC pass each, kernel-trace only)
 bash "$R/tools/pmc_sq.sh" xconv xconv_kernel -- python "$R/tools/bench_vae_exact.py" 16 > "$O/pmc_sq_xconv.log" 2>&1
 cp "$R/gpurun_out/pmc_sq_xconv/summary.json" "$O/r4_pmc_sq_xconv.json"
