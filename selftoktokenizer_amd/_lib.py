@@ -1,4 +1,4 @@
-"""ctypes loader for libselftok_hip.so (the C ABI of include/selftok_hip.h).
+"""ctypes loader for libselftok_hip.so (the C ABI of include/selftok_hip.h and include/selftok_hip_ext.h).
 
 No fallback: if the library is missing or a symbol is absent this raises -- the product path must
 fail loudly rather than silently run something else.
@@ -80,6 +80,12 @@ SIGNATURES = {
 }
 
 
+# entries of include/selftok_hip_ext.h: exported by libselftok_hip.so only (no CPU twin yet)
+EXT_SIGNATURES = {
+    "selftok_attn_kmask_f32": (_i, [_vp, _vp, _l, _vp]),
+}
+
+
 class AttnSeg(C.Structure):
     _fields_ = [("q", _vp), ("k", _vp), ("v", _vp), ("o", _vp), ("len", _i),
                 ("q_rs", _l), ("k_rs", _l), ("v_rs", _l), ("o_rs", _l),
@@ -106,7 +112,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the .so is stale
             fn.restype = res
             fn.argtypes = args

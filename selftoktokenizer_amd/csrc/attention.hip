@@ -22,6 +22,7 @@
 // K tiles are staged [key][68] (b128 reads, conflict-free), V tiles [key][64] (b32 reads, conflict-free).
 #include "common.h"
 #include "selftok_hip.h"
+#include "selftok_hip_ext.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -49,12 +50,56 @@ struct AttnParams {
     int qtiles;             // 128-row query tiles per (sample, head), both segments
     int xcd_remap;
     int prio;               // attn64_dma_kernel: raise the wave's issue priority inside its MFMA clusters (s_setprio)
+    const unsigned* kmask;  // <true> instantiations: [B, kmask_bs] words, bit j & 31 of word j >> 5 = segment-0 key j is visible
+    long kmask_bs;
 };
 
 constexpr int KT = 32;           // keys per tile
 constexpr int KSTR = 68;         // padded K row stride in LDS (floats)
 constexpr int QROWS = 128;       // query rows per workgroup
 
+// ---------------------------------------------------------------------------------------
+// Per-sample key bit mask (selftok_attn_kmask_f32, include/selftok_hip_ext.h).  The three head_dim-64 kernels below are templates on
+// KMASK; the <false> instantiations are the kernels of selftok_attn_f32 and contain none of this (`if constexpr`).
+//   * lane i of every wave holds word i of the sample (bits >= seg[0].len cleared): one vector load per wave, after which a
+//     tile's word is a v_readlane into an SGPR and the set of tiles with a visible key is one 64-bit ballot.
+//   * tiles whose word is 0 are never staged or multiplied: the walk pops the next set bit of that ballot.
+//   * a tile's word doubles as the ragged-tile mask (bits past the end of the segment are clear), so a full word takes the
+//     unmasked path and anything else the wave-uniform "ragged tile" branch.
+//   * a segment-0 query row whose bit is clear is dead: not stored; a wave whose 32 rows are dead stages and synchronises but
+//     issues no MFMA; a workgroup whose 128 rows are dead returns before any q / k / v load.
+// ---------------------------------------------------------------------------------------
+struct KMaskWalk {
+    unsigned wv;                  // lane i: word i
+    unsigned long long rem;       // segment-0 tiles with a visible key that are not staged yet
+    unsigned roww;                // visibility word of this wave's 32 query rows (all ones for segment-1 rows)
+    int cur, nxt;                 // segment-0 tile being consumed / being staged
+    __device__ __forceinline__ int pop() { const int i = __builtin_ctzll(rem); rem &= rem - 1; return i; }
+    __device__ __forceinline__ unsigned word(int i) const { return (unsigned)__builtin_amdgcn_readlane((int)wv, i); }
+};
+// -> false: every query row of this workgroup is dead
+__device__ __forceinline__ bool kmask_init(KMaskWalk& M, const unsigned* __restrict__ kmask, long kmask_bs, int b, int len0, int s, int r0, int wave, int lane)
+{
+    const int nw = (len0 + 31) >> 5;                          // <= 64, checked by the launcher
+    M.wv = 0;
+    if (lane < nw) {
+        M.wv = kmask[(size_t)b * kmask_bs + lane];
+        if (lane == nw - 1 && (len0 & 31)) M.wv &= (1u << (len0 & 31)) - 1u;
+    }
+    M.rem = __ballot(M.wv != 0);
+    M.roww = ~0u; M.cur = 0; M.nxt = 0;
+    if (s == 0) {
+        const int w0 = r0 >> 5;                               // r0 < len0: w0 < nw
+        if (((M.rem >> w0) & 0xfull) == 0) return false;
+        const int wi = w0 + __builtin_amdgcn_readfirstlane(wave);
+        M.roww = wi < nw ? M.word(wi) : 0u;
+    }
+    return true;
+}
+// visibility word of a tile without a mask: all ones, or the low bits of a ragged last tile
+__device__ __forceinline__ unsigned ragged_word(int key0, int nkeys) { return key0 + KT > nkeys ? (1u << (nkeys - key0)) - 1u : ~0u; }
+
+template <bool KMASK>
 __global__ __launch_bounds__(256) void attn64_kernel(AttnParams P)
 {
     // K and V tiles, double buffered: tile t+1 is written while tile t is being consumed -> one barrier per tile
@@ -87,16 +132,24 @@ __global__ __launch_bounds__(256) void attn64_kernel(AttnParams P)
     }
     const int rows_live = (s == 0) ? rows0 : (P.seg[1].q ? P.seg[1].len : 0);
     if (r0 >= rows_live) return;                            // dead context rows / empty tile
+    KMaskWalk M;
+    if constexpr (KMASK) { if (!kmask_init(M, P.kmask, P.kmask_bs, b, P.seg[0].len, s, r0, wave, lane)) return; }
 
     const AttnSeg& qs = P.seg[s];
     const int n1 = (s == 1 || P.seg0_sees_seg1) ? P.seg[1].len : 0;
 
     // ---- Q fragments: lane (half, col) holds Q[row][dd = m + 32*half], m = 0..31 ----
     const int my_row = r0 + wave * 32 + col;
-    const bool row_ok = my_row < rows_live;
+    bool row_ok = my_row < rows_live;
+    int q_row = row_ok ? my_row : (rows_live - 1);
+    if constexpr (KMASK) {                                  // a dead row (inside the segment) computes on the q of a live row of its wave and is not stored
+        const bool dead = row_ok && !((M.roww >> col) & 1u);
+        if (dead && M.roww != 0) q_row = r0 + __builtin_amdgcn_readfirstlane(wave) * 32 + __builtin_ctz(M.roww);   // a set bit of roww is a row < len
+        row_ok = row_ok && !dead;
+    }
     float qf[32];
     {
-        const float* qp = qs.q + (size_t)b * qs.q_bs + (size_t)(row_ok ? my_row : (rows_live - 1)) * qs.q_rs + h * 64 + 32 * half;
+        const float* qp = qs.q + (size_t)b * qs.q_bs + (size_t)q_row * qs.q_rs + h * 64 + 32 * half;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float4 t = *reinterpret_cast<const float4*>(qp + 4 * j);
@@ -118,18 +171,25 @@ __global__ __launch_bounds__(256) void attn64_kernel(AttnParams P)
     const float* kp = nullptr;
     const float* vp = nullptr;
     long k_step = 0, v_step = 0, k_half = 0, v_half = 0;
+    int ptile = 0;                                          // KMASK: the tile the running pointers stand at
     auto set_segment = [&](int seg) {
         const AttnSeg& ks = P.seg[seg];
         kp = ks.k + (size_t)b * ks.k_bs + (size_t)st_key * ks.k_rs + h * 64 + st_part * 4;
         vp = ks.v + (size_t)b * ks.v_bs + (size_t)st_key * ks.v_rs + h * 64 + st_part * 4;
         k_step = (long)KT * ks.k_rs; v_step = (long)KT * ks.v_rs;
         k_half = 16 * ks.k_rs; v_half = 16 * ks.v_rs;
+        if constexpr (KMASK) ptile = 0;
     };
-    auto issue_loads = [&](int key0, int nkeys) {
+    auto issue_loads = [&](int key0, int nkeys, unsigned wm) {
+        if constexpr (KMASK) {
+            const int ti = key0 / KT;
+            kp += (long)(ti - ptile) * k_step; vp += (long)(ti - ptile) * v_step;
+            ptile = ti + 1;
+        }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             int key = key0 + st_key + 16 * u;
-            if (key < nkeys) {
+            if (KMASK ? ((wm >> (st_key + 16 * u)) & 1u) != 0 : key < nkeys) {
                 rk[u] = *reinterpret_cast<const float4*>(kp + u * k_half);
                 rv[u] = *reinterpret_cast<const float4*>(vp + u * v_half);
             } else {
@@ -141,11 +201,14 @@ __global__ __launch_bounds__(256) void attn64_kernel(AttnParams P)
     };
 
     // flattened tile list: segment 0 keys [0,n0) then segment 1 keys [0,n1)
-    const int nt0 = (n0 + KT - 1) / KT, nt1 = (n1 + KT - 1) / KT;
+    const int nt0 = KMASK ? __builtin_popcountll(M.rem) : (n0 + KT - 1) / KT, nt1 = (n1 + KT - 1) / KT;
     const int ntiles = nt0 + nt1;
     if (ntiles == 0) return;
     set_segment(nt0 > 0 ? 0 : 1);
-    issue_loads(0, nt0 > 0 ? n0 : n1);
+    if constexpr (KMASK) {
+        if (nt0 > 0) { M.cur = M.pop(); issue_loads(M.cur * KT, n0, M.word(M.cur)); }
+        else issue_loads(0, n1, ragged_word(0, n1));
+    } else issue_loads(0, nt0 > 0 ? n0 : n1, 0u);
     auto write_tile = [&](int buf) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -156,18 +219,36 @@ __global__ __launch_bounds__(256) void attn64_kernel(AttnParams P)
     };
     write_tile(0);
     __syncthreads();
+    auto load_next = [&](int t) {                            // KMASK: the loads of the tile after walk position t
+        if (t + 1 < nt0) { M.nxt = M.pop(); issue_loads(M.nxt * KT, n0, M.word(M.nxt)); }
+        else issue_loads((t + 1 - nt0) * KT, n1, ragged_word((t + 1 - nt0) * KT, n1));
+    };
+    if constexpr (KMASK)
+        if (M.roww == 0) {                                   // a wave of dead rows: its share of the staging and the barriers, no MFMA
+            for (int t = 0; t + 1 < ntiles; ++t) {
+                if (t + 1 == nt0) set_segment(1);
+                load_next(t);
+                write_tile((t + 1) & 1);
+                __syncthreads();
+            }
+            __syncthreads();
+            return;
+        }
 
     for (int t = 0; t < ntiles; ++t) {
         const int seg = t < nt0 ? 0 : 1;
-        const int key0 = (seg == 0 ? t : t - nt0) * KT;
+        const int key0 = (seg == 0 ? (KMASK ? M.cur : t) : t - nt0) * KT;
         const int nkeys = seg == 0 ? n0 : n1;
         const float* s_k = s_kb[t & 1];
         const float* s_v = s_vb[t & 1];
         if (t + 1 < ntiles) {                                // global loads of the next tile fly behind this tile's MFMAs
             const int seg_n = (t + 1) < nt0 ? 0 : 1;
             if (t + 1 == nt0) set_segment(1);                // first tile of segment 1
-            issue_loads((seg_n == 0 ? t + 1 : t + 1 - nt0) * KT, seg_n == 0 ? n0 : n1);
+            if constexpr (KMASK) load_next(t);
+            else issue_loads((seg_n == 0 ? t + 1 : t + 1 - nt0) * KT, seg_n == 0 ? n0 : n1, 0u);
         }
+        unsigned wm = ~0u;                                   // KMASK: visibility word of this tile
+        if constexpr (KMASK) wm = seg == 0 ? M.word(M.cur) : ragged_word(key0, nkeys);
 
         // ---- S^T[key][q] = sum_dd K[key][dd] Q[q][dd] ----
         f32x16 sc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -180,6 +261,15 @@ __global__ __launch_bounds__(256) void attn64_kernel(AttnParams P)
             sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[4 * j + 3], sc, 0, 0, 0);
         }
         // sc[r] = S[q = col][key = key0 + (r&3) + 8*(r>>2) + 4*half]
+        if constexpr (KMASK) {
+            if (wm != ~0u) {                                 // mixed word (or ragged tile): the same wave-uniform branch as below
+                asm volatile("; masked tile");
+                const unsigned wl = wm >> (4 * half);
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (!((wl >> ((r & 3) + 8 * (r >> 2))) & 1u)) sc[r] = -__builtin_inff();
+            }
+        } else
         if (key0 + KT > nkeys) {                             // ragged last tile: mask the padding keys
             // the empty volatile asm keeps this block a real (wave-uniform) branch: hipcc otherwise if-converts it into 16 x
             // (v_subrev, v_cmp, v_cndmask) executed on EVERY tile -- 48 VALU ops beside the fp32 MFMAs for one tile per segment
@@ -224,6 +314,7 @@ __global__ __launch_bounds__(256) void attn64_kernel(AttnParams P)
             o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, sc[m], o0, 0, 0, 0);
             o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, sc[m], o1, 0, 0, 0);
         }
+        if constexpr (KMASK) M.cur = M.nxt;
         if (t + 1 < ntiles) write_tile((t + 1) & 1);        // that buffer was last read in iteration t-1 (barrier below)
         __syncthreads();
     }
@@ -262,6 +353,7 @@ __device__ __forceinline__ void attn_lds_dma16(const void* base, unsigned voff, 
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds) : "memory", "m0");
 }
 
+template <bool KMASK>
 __global__ __launch_bounds__(256) void attn64_dma_kernel(AttnParams P)
 {
     __shared__ __attribute__((aligned(1024))) float s_kb[2][KT * 64];     // swizzled rows, see above
@@ -290,14 +382,22 @@ __global__ __launch_bounds__(256) void attn64_dma_kernel(AttnParams P)
     }
     const int rows_live = (s == 0) ? rows0 : (P.seg[1].q ? P.seg[1].len : 0);
     if (r0 >= rows_live) return;
+    KMaskWalk M;
+    if constexpr (KMASK) { if (!kmask_init(M, P.kmask, P.kmask_bs, b, P.seg[0].len, s, r0, wave, lane)) return; }
     const AttnSeg& qs = P.seg[s];
     const int n1 = (s == 1 || P.seg0_sees_seg1) ? P.seg[1].len : 0;
 
     const int my_row = r0 + wave * 32 + col;
-    const bool row_ok = my_row < rows_live;
+    bool row_ok = my_row < rows_live;
+    int q_row = row_ok ? my_row : (rows_live - 1);
+    if constexpr (KMASK) {                                  // a dead row (inside the segment) computes on the q of a live row of its wave and is not stored
+        const bool dead = row_ok && !((M.roww >> col) & 1u);
+        if (dead && M.roww != 0) q_row = r0 + wave * 32 + __builtin_ctz(M.roww);   // a set bit of roww is a row < len
+        row_ok = row_ok && !dead;
+    }
     float qf[32];
     {
-        const float* qp = qs.q + (size_t)b * qs.q_bs + (size_t)(row_ok ? my_row : (rows_live - 1)) * qs.q_rs + h * 64 + 32 * half;
+        const float* qp = qs.q + (size_t)b * qs.q_bs + (size_t)q_row * qs.q_rs + h * 64 + 32 * half;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float4 t = *reinterpret_cast<const float4*>(qp + 4 * j);
@@ -314,12 +414,12 @@ __global__ __launch_bounds__(256) void attn64_dma_kernel(AttnParams P)
     const int ksw = pos ^ ((4 * wave + kr) & 15);              // source chunk of that position (pieces w and w + 4: same rows mod 16)
     const unsigned lds_k = (unsigned)(size_t)(__attribute__((address_space(3))) float*)&s_kb[0][0];
     const unsigned lds_v = (unsigned)(size_t)(__attribute__((address_space(3))) float*)&s_vb[0][0];
-    auto stage = [&](int seg, int key0, int nkeys, int buf) {
+    auto stage = [&](int seg, int key0, int nkeys, int buf, unsigned wm) {     // wm (KMASK): visibility word of the tile
         const AttnSeg& ks = P.seg[seg];
         const char* kb = reinterpret_cast<const char*>(ks.k + (size_t)b * ks.k_bs + (size_t)key0 * ks.k_rs + h * 64);
         const char* vb = reinterpret_cast<const char*>(ks.v + (size_t)b * ks.v_bs + (size_t)key0 * ks.v_rs + h * 64);
         const unsigned krs = (unsigned)ks.k_rs * 4u, vrs = (unsigned)ks.v_rs * 4u;
-        if (key0 + KT <= nkeys) {                              // full tile: uniform bases, constant per-lane offsets
+        if (KMASK ? wm == ~0u : key0 + KT <= nkeys) {          // full tile: uniform bases, constant per-lane offsets
             const unsigned ko = kr * krs + ksw * 16, vo = kr * vrs + pos * 16;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -329,10 +429,11 @@ __global__ __launch_bounds__(256) void attn64_dma_kernel(AttnParams P)
             }
         } else {                                               // ragged last tile of the segment: clamp the source row per lane
             const int last = nkeys - 1 - key0;                 // >= 0
+            const int first = KMASK ? __builtin_ctz(wm) : 0;   // KMASK: an invisible key is fetched from the tile's first visible key (wm != 0)
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int i = wave + 4 * u;
-                const int row = 4 * i + kr, src = row < last ? row : last;
+                const int row = 4 * i + kr, src = KMASK ? (((wm >> row) & 1u) ? row : first) : (row < last ? row : last);
                 attn_lds_dma16(kb, (unsigned)src * krs + ksw * 16, lds_k + buf * (KT * 256) + i * 1024);
                 attn_lds_dma16(vb, (unsigned)src * vrs + pos * 16, lds_v + buf * (KT * 256) + i * 1024);
             }
@@ -343,25 +444,47 @@ __global__ __launch_bounds__(256) void attn64_dma_kernel(AttnParams P)
 #pragma unroll
     for (int j = 0; j < 8; ++j) kaddr[j] = col * 64 + (((8 * half + j) ^ (col & 15)) << 2);
 
-    const int nt0 = (n0 + KT - 1) / KT, nt1 = (n1 + KT - 1) / KT;
+    const int nt0 = KMASK ? __builtin_popcountll(M.rem) : (n0 + KT - 1) / KT, nt1 = (n1 + KT - 1) / KT;
     const int ntiles = nt0 + nt1;
     if (ntiles == 0) return;
-    stage(nt0 > 0 ? 0 : 1, 0, nt0 > 0 ? n0 : n1, 0);
+    if constexpr (KMASK) {
+        if (nt0 > 0) { M.cur = M.pop(); stage(0, M.cur * KT, n0, 0, M.word(M.cur)); }
+        else stage(1, 0, n1, 0, ragged_word(0, n1));
+    } else stage(nt0 > 0 ? 0 : 1, 0, nt0 > 0 ? n0 : n1, 0, 0u);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    auto stage_next = [&](int t, int bufn) {                 // KMASK: the DMAs of the tile after walk position t
+        if (t + 1 < nt0) { M.nxt = M.pop(); stage(0, M.nxt * KT, n0, bufn, M.word(M.nxt)); }
+        else stage(1, (t + 1 - nt0) * KT, n1, bufn, ragged_word((t + 1 - nt0) * KT, n1));
+    };
+    if constexpr (KMASK)
+        if (M.roww == 0) {                                   // a wave of dead rows: its share of the staging and the barriers, no MFMA
+            for (int t = 0; t < ntiles; ++t) {
+                if (t + 1 < ntiles) stage_next(t, (t & 1) ^ 1);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+            return;
+        }
 
     // one 32-key tile; BUF (the LDS buffer it sits in) is a compile-time constant so that every fragment read is
     // (tile-invariant address register) + (immediate offset): with a run-time buffer index hipcc spends a v_or + v_add per read
     auto tile = [&](int t, auto BUF) {
         constexpr int buf = decltype(BUF)::value;
         const int seg = t < nt0 ? 0 : 1;
-        const int key0 = (seg == 0 ? t : t - nt0) * KT;
+        const int key0 = (seg == 0 ? (KMASK ? M.cur : t) : t - nt0) * KT;
         const int nkeys = seg == 0 ? n0 : n1;
         const float* s_k = s_kb[buf];
         const float* s_v = s_vb[buf];
         if (t + 1 < ntiles) {                                // the next tile's DMAs fly behind this tile's MFMAs
             const int seg_n = (t + 1) < nt0 ? 0 : 1;
-            stage(seg_n, (seg_n == 0 ? t + 1 : t + 1 - nt0) * KT, seg_n == 0 ? n0 : n1, buf ^ 1);
+            if constexpr (KMASK) stage_next(t, buf ^ 1);
+            else stage(seg_n, (seg_n == 0 ? t + 1 : t + 1 - nt0) * KT, seg_n == 0 ? n0 : n1, buf ^ 1, 0u);
+        }
+        unsigned wm = ~0u;                                   // KMASK: visibility word of this tile
+        if constexpr (KMASK) {
+            wm = seg == 0 ? M.word(M.cur) : ragged_word(key0, nkeys);
+            M.cur = M.nxt;
         }
 
         f32x16 sc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -375,6 +498,15 @@ __global__ __launch_bounds__(256) void attn64_dma_kernel(AttnParams P)
             sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[4 * j + 3], sc, 0, 0, 0);
         }
         if (prio) __builtin_amdgcn_s_setprio(0);
+        if constexpr (KMASK) {
+            if (wm != ~0u) {                                 // mixed word (or ragged tile): the same wave-uniform branch as below
+                asm volatile("; masked tile");
+                const unsigned wl = wm >> (4 * half);
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (!((wl >> ((r & 3) + 8 * (r >> 2))) & 1u)) sc[r] = -__builtin_inff();
+            }
+        } else
         if (key0 + KT > nkeys) {
             asm volatile("; ragged tile");                   // a real branch, not 48 if-converted VALU ops per tile (see attn64_kernel)
 #pragma unroll
@@ -498,6 +630,7 @@ __device__ __forceinline__ HiLo split_pair_kv(float a, float b)
 __device__ __forceinline__ HiLo split_pair_kv(float a, float b) { return split_pair(a, b); }
 #endif
 
+template <bool KMASK>
 __global__ __launch_bounds__(256, 2) void attn64_f16x2_kernel(AttnParams P, int* __restrict__ overflow)
 {
     __shared__ __attribute__((aligned(16))) unsigned char s_kv[2 * KV_BUF];
@@ -524,6 +657,8 @@ __global__ __launch_bounds__(256, 2) void attn64_f16x2_kernel(AttnParams P, int*
     }
     const int rows_live = (s == 0) ? rows0 : (P.seg[1].q ? P.seg[1].len : 0);
     if (r0 >= rows_live) return;
+    KMaskWalk M;
+    if constexpr (KMASK) { if (!kmask_init(M, P.kmask, P.kmask_bs, b, P.seg[0].len, s, r0, wave, lane)) return; }
     const AttnSeg& qs = P.seg[s];
     const int n1 = (s == 1 || P.seg0_sees_seg1) ? P.seg[1].len : 0;
 
@@ -531,10 +666,16 @@ __global__ __launch_bounds__(256, 2) void attn64_f16x2_kernel(AttnParams P, int*
     // by scale * log2(e) so that the scores come out of the matrix pipe in the log2 domain ----
     const float c = P.scale * 1.4426950408889634f;
     const int my_row = r0 + wave * 32 + col;
-    const bool row_ok = my_row < rows_live;
+    bool row_ok = my_row < rows_live;
+    int q_row = row_ok ? my_row : (rows_live - 1);
+    if constexpr (KMASK) {                                  // a dead row (inside the segment) computes on the q of a live row of its wave and is not stored
+        const bool dead = row_ok && !((M.roww >> col) & 1u);
+        if (dead && M.roww != 0) q_row = r0 + __builtin_amdgcn_readfirstlane(wave) * 32 + __builtin_ctz(M.roww);   // a set bit of roww is a row < len
+        row_ok = row_ok && !dead;
+    }
     u32x4 q0[4], q1[4];
     {
-        const float* qp = qs.q + (size_t)b * qs.q_bs + (size_t)(row_ok ? my_row : (rows_live - 1)) * qs.q_rs + h * 64 + 8 * half;
+        const float* qp = qs.q + (size_t)b * qs.q_bs + (size_t)q_row * qs.q_rs + h * 64 + 8 * half;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const float4 a = *reinterpret_cast<const float4*>(qp + 16 * ks);
@@ -559,20 +700,27 @@ __global__ __launch_bounds__(256, 2) void attn64_f16x2_kernel(AttnParams P, int*
     float4 rg[4];
     const float* sp = nullptr;         // running pointer: row key0 + st_key of the next tile to load
     long s_rs = 0;
+    int ptile = 0;                     // KMASK: the tile the running pointer stands at
     auto set_segment = [&](int seg) {
         const AttnSeg& ks = P.seg[seg];
         if (is_k) { sp = ks.k + (size_t)b * ks.k_bs + (size_t)st_key * ks.k_rs + h * 64 + st_d; s_rs = ks.k_rs; }
         else { sp = ks.v + (size_t)b * ks.v_bs + (size_t)st_key * ks.v_rs + h * 64 + st_d; s_rs = ks.v_rs; }
+        if constexpr (KMASK) ptile = 0;
     };
-    auto issue_loads = [&](int key0, int nkeys) {
+    auto issue_loads = [&](int key0, int nkeys, unsigned wm) {     // wm (KMASK): visibility word of the tile; an invisible key is staged as zeros
+        if constexpr (KMASK) {
+            const int ti = key0 / KT;
+            sp += (long)(ti - ptile) * KT * s_rs;
+            ptile = ti + 1;
+        }
         if (is_k) {
-            const bool ok = key0 + st_key < nkeys;
+            const bool ok = KMASK ? ((wm >> st_key) & 1u) != 0 : key0 + st_key < nkeys;
 #pragma unroll
             for (int i = 0; i < 4; ++i) rg[i] = ok ? *reinterpret_cast<const float4*>(sp + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                rg[i] = (key0 + st_key + i < nkeys) ? *reinterpret_cast<const float4*>(sp + i * s_rs) : make_float4(0.f, 0.f, 0.f, 0.f);
+                rg[i] = (KMASK ? ((wm >> (st_key + i)) & 1u) != 0 : key0 + st_key + i < nkeys) ? *reinterpret_cast<const float4*>(sp + i * s_rs) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         sp += (long)KT * s_rs;
     };
@@ -608,23 +756,47 @@ __global__ __launch_bounds__(256, 2) void attn64_f16x2_kernel(AttnParams P, int*
         }
     };
 
-    const int nt0 = (n0 + KT - 1) / KT, nt1 = (n1 + KT - 1) / KT;
+    const int nt0 = KMASK ? __builtin_popcountll(M.rem) : (n0 + KT - 1) / KT, nt1 = (n1 + KT - 1) / KT;
     const int ntiles = nt0 + nt1;
     if (ntiles == 0) return;
     set_segment(nt0 > 0 ? 0 : 1);
-    issue_loads(0, nt0 > 0 ? n0 : n1);
+    if constexpr (KMASK) {
+        if (nt0 > 0) { M.cur = M.pop(); issue_loads(M.cur * KT, n0, M.word(M.cur)); }
+        else issue_loads(0, n1, ragged_word(0, n1));
+    } else issue_loads(0, nt0 > 0 ? n0 : n1, 0u);
     write_tile(0);
     __syncthreads();
+    auto load_next = [&](int t) {                            // KMASK: the loads of the tile after walk position t
+        if (t + 1 < nt0) { M.nxt = M.pop(); issue_loads(M.nxt * KT, n0, M.word(M.nxt)); }
+        else issue_loads((t + 1 - nt0) * KT, n1, ragged_word((t + 1 - nt0) * KT, n1));
+    };
+    if constexpr (KMASK)
+        if (M.roww == 0) {                                   // a wave of dead rows: its share of the staging and the barriers, no MFMA
+            for (int t = 0; t + 1 < ntiles; ++t) {
+                if (t + 1 == nt0) set_segment(1);
+                load_next(t);
+                write_tile((t + 1) & 1);
+                __syncthreads();
+            }
+            __syncthreads();
+            return;
+        }
 
     for (int t = 0; t < ntiles; ++t) {
         const int seg = t < nt0 ? 0 : 1;
-        const int key0 = (seg == 0 ? t : t - nt0) * KT;
+        const int key0 = (seg == 0 ? (KMASK ? M.cur : t) : t - nt0) * KT;
         const int nkeys = seg == 0 ? n0 : n1;
         const unsigned char* sb = s_kv + (t & 1) * KV_BUF;
         if (t + 1 < ntiles) {
             const int seg_n = (t + 1) < nt0 ? 0 : 1;
             if (t + 1 == nt0) set_segment(1);
-            issue_loads((seg_n == 0 ? t + 1 : t + 1 - nt0) * KT, seg_n == 0 ? n0 : n1);
+            if constexpr (KMASK) load_next(t);
+            else issue_loads((seg_n == 0 ? t + 1 : t + 1 - nt0) * KT, seg_n == 0 ? n0 : n1, 0u);
+        }
+        unsigned wm = ~0u;                                   // KMASK: visibility word of this tile
+        if constexpr (KMASK) {
+            wm = seg == 0 ? M.word(M.cur) : ragged_word(key0, nkeys);
+            M.cur = M.nxt;
         }
 
         // ---- S^T[key][q] = sum_d K[key][d] Q'[q][d]: 4 k-steps of 16 d, three f16 MFMAs each ----
@@ -638,6 +810,15 @@ __global__ __launch_bounds__(256, 2) void attn64_f16x2_kernel(AttnParams P, int*
             sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, as_h8(q0[ks]), sc, 0, 0, 0);
         }
         // sc[r] = log2(e) * scale * S[q = col][key = key0 + (r&3) + 8*(r>>2) + 4*half]
+        if constexpr (KMASK) {
+            if (wm != ~0u) {                                 // mixed word (or ragged tile): the same wave-uniform branch as below
+                asm volatile("; masked tile");
+                const unsigned wl = wm >> (4 * half);
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (!((wl >> ((r & 3) + 8 * (r >> 2))) & 1u)) sc[r] = -__builtin_inff();
+            }
+        } else
         if (key0 + KT > nkeys) {
             asm volatile("; ragged tile");                   // a real branch, not 48 if-converted VALU ops per tile (see attn64_kernel)
 #pragma unroll
@@ -777,11 +958,16 @@ __global__ __launch_bounds__(256) void attn16_kernel(const float* __restrict__ q
 
 using namespace selftok;
 
-extern "C" {
-
-int selftok_attn_f32(const selftok_attn_desc* d, hipStream_t stream)
+// selftok_attn_f32 (kmask == NULL) and selftok_attn_kmask_f32: the same checks and the same dispatch, onto the masked instantiations
+static int attn_launch(const selftok_attn_desc* d, const unsigned* kmask, long kmask_bs, hipStream_t stream)
 {
     if (!d || d->B < 0 || d->H <= 0) { set_last_error("attn: bad descriptor"); return SELFTOK_EINVAL; }
+    if (kmask) {
+        if (d->kvis) { set_last_error("attn(kmask): kvis and kmask are exclusive"); return SELFTOK_EINVAL; }
+        if (d->head_dim != 64) { set_last_error("attn(kmask): head_dim 64 only"); return SELFTOK_EINVAL; }
+        if (d->seg[0].len > 64 * KT) { set_last_error("attn(kmask): segment 0 has more than 2048 keys (64 mask words)"); return SELFTOK_EINVAL; }
+        if (((size_t)kmask & 3) != 0 || kmask_bs < (d->seg[0].len + KT - 1) / KT) { set_last_error("attn(kmask): kmask_bs < ceil(seg[0].len / 32) or unaligned mask"); return SELFTOK_EINVAL; }
+    }
     if (d->B == 0) return SELFTOK_OK;
     if (d->head_dim == 64) {
         AttnParams P;
@@ -800,11 +986,16 @@ int selftok_attn_f32(const selftok_attn_desc* d, hipStream_t stream)
         P.qtiles = t0 + t1;
         P.xcd_remap = 1;
         P.prio = 0;
+        P.kmask = kmask; P.kmask_bs = kmask_bs;
 #ifdef SELFTOK_TUNE
         { const char* e = getenv("SELFTOK_ATTN_PRIO"); if (e) P.prio = atoi(e); }
 #endif
         if (d->mode == SELFTOK_ATTN_F16X2) {
-            hipLaunchKernelGGL(attn64_f16x2_kernel, dim3((t0 + t1) * d->H * d->B), dim3(256), 0, stream, P, d->overflow);
+            if (kmask) {
+                hipLaunchKernelGGL(attn64_f16x2_kernel<true>, dim3((t0 + t1) * d->H * d->B), dim3(256), 0, stream, P, d->overflow);
+                return check_launch("attn64_f16x2_kernel<kmask>");
+            }
+            hipLaunchKernelGGL(attn64_f16x2_kernel<false>, dim3((t0 + t1) * d->H * d->B), dim3(256), 0, stream, P, d->overflow);
             return check_launch("attn64_f16x2_kernel");
         }
         if (d->mode != 0) { set_last_error("attn: unknown mode"); return SELFTOK_EINVAL; }
@@ -815,11 +1006,16 @@ int selftok_attn_f32(const selftok_attn_desc* d, hipStream_t stream)
 #ifdef SELFTOK_TUNE
         { const char* e = getenv("SELFTOK_ATTN_VARIANT"); if (e && atoi(e) == 0) dma = false; }      // 0: register-staged kernel of rounds 1-2
 #endif
+        if (kmask) {
+            if (dma) hipLaunchKernelGGL(attn64_dma_kernel<true>, dim3((t0 + t1) * d->H * d->B), dim3(256), 0, stream, P);
+            else hipLaunchKernelGGL(attn64_kernel<true>, dim3((t0 + t1) * d->H * d->B), dim3(256), 0, stream, P);
+            return check_launch(dma ? "attn64_dma_kernel<kmask>" : "attn64_kernel<kmask>");
+        }
         if (dma) {
-            hipLaunchKernelGGL(attn64_dma_kernel, dim3((t0 + t1) * d->H * d->B), dim3(256), 0, stream, P);
+            hipLaunchKernelGGL(attn64_dma_kernel<false>, dim3((t0 + t1) * d->H * d->B), dim3(256), 0, stream, P);
             return check_launch("attn64_dma_kernel");
         }
-        hipLaunchKernelGGL(attn64_kernel, dim3((t0 + t1) * d->H * d->B), dim3(256), 0, stream, P);
+        hipLaunchKernelGGL(attn64_kernel<false>, dim3((t0 + t1) * d->H * d->B), dim3(256), 0, stream, P);
         return check_launch("attn64_kernel");
     }
     if (d->head_dim == 16) {
@@ -833,6 +1029,16 @@ int selftok_attn_f32(const selftok_attn_desc* d, hipStream_t stream)
     }
     set_last_error("attn: head_dim must be 64 or 16");
     return SELFTOK_EINVAL;
+}
+
+extern "C" {
+
+int selftok_attn_f32(const selftok_attn_desc* d, hipStream_t stream) { return attn_launch(d, nullptr, 0, stream); }
+
+int selftok_attn_kmask_f32(const selftok_attn_desc* d, const unsigned* kmask, long kmask_bs, hipStream_t stream)
+{
+    if (!kmask) { set_last_error("attn(kmask): kmask is NULL (selftok_attn_f32 is the unmasked entry)"); return SELFTOK_EINVAL; }
+    return attn_launch(d, kmask, kmask_bs, stream);
 }
 
 }  // extern "C"

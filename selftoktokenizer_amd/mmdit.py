@@ -261,9 +261,11 @@ class MMDiTGPU(ModuleSurface):
 
     @torch.no_grad()
     def core(self, xe: torch.Tensor, c: Optional[torch.Tensor], ctx: Optional[torch.Tensor], seg0_sees_seg1: bool = True,
-             kvis: Optional[torch.Tensor] = None, cqkv0: Optional[torch.Tensor] = None, tables=None, mods=None) -> torch.Tensor:
+             kvis: Optional[torch.Tensor] = None, cqkv0: Optional[torch.Tensor] = None, tables=None, mods=None,
+             kmask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """xe [B,n_x,H] embedded image tokens, c [B,H], ctx [B,n_ctx,H] live context tokens (or None / n_ctx = 0)
-        -> FinalLayer output [B,n_x,64] (before unpatchify).  `tables`: per-block context adaLN tables whose row j belongs to context
+        -> FinalLayer output [B,n_x,64] (before unpatchify).  `kmask`: int32 [B, W] words of a per-sample visibility pattern over the
+        context rows (`pack_key_mask`; exclusive with kvis; bits past n_ctx are ignored), the same words for all 24 blocks.  `tables`: per-block context adaLN tables whose row j belongs to context
         row j (default: the position tables; `gather_context` returns the rows of a visibility pattern).  `mods`: the result of
         `modulations(c, ...)` if the caller already has it (c is then unused)."""
         H, NH = DIT_HIDDEN, DIT_HEADS
@@ -292,8 +294,8 @@ class MMDiTGPU(ModuleSurface):
                 # the joint attention as ATen's fp32 flash kernel evaluates `attention(q, k, v, heads, mask)` (sd3/other_impls.py:37-45) on the
                 # FULL key sequence [K context slots | image tokens] with the prefix mask: the n live context keys keep their positions (kv blocks
                 # of 512, MKL's K-blocks of 256 inside), the masked ones contribute exact zeros -- the same bits, not the truncated sequence's
-                if kvis is not None:
-                    raise NotImplementedError("gemm='exact': one visibility prefix per call (the sampler's case); a per-sample `kvis` needs gemm='fp32' / 'f16x2'")
+                if kvis is not None or kmask is not None:
+                    raise NotImplementedError("gemm='exact': one visibility prefix per call (the sampler's case); a per-sample `kvis` / `kmask` needs gemm='fp32' / 'f16x2'")
                 xk, xv = xqkv[..., H:2 * H], xqkv[..., 2 * H:]
                 if has_ctx:
                     cqkv = cqkv0[:, :n].contiguous() if (i == 0 and cqkv0 is not None) else self.lin(pc + ".attn.qkv", cn)
@@ -313,9 +315,9 @@ class MMDiTGPU(ModuleSurface):
                 if last:   # pre_only context block: keys/values only, its attention output is discarded (sd3/mmdit.py:544-547)
                     seg0 = (None, cqkv[..., H:2 * H], cqkv[..., 2 * H:], None)
                 else:
-                    oc = attn_out(n, pc + ".attn.proj", zero=kvis is not None)
+                    oc = attn_out(n, pc + ".attn.proj", zero=kvis is not None or kmask is not None)
                     seg0 = (cqkv[..., :H], cqkv[..., H:2 * H], cqkv[..., 2 * H:], oc)
-                ops.attention(seg0, seg1, NH, 64, kvis=kvis, seg0_sees_seg1=seg0_sees_seg1, mode=amode, overflow=self.overflow)
+                ops.attention(seg0, seg1, NH, 64, kvis=kvis, seg0_sees_seg1=seg0_sees_seg1, mode=amode, overflow=self.overflow, kmask=kmask)
             else:
                 ops.attention(None, seg1, NH, 64, mode=amode, overflow=self.overflow)
             # ---- context stream post-attention (sd3/mmdit.py:485-496, 'pos_emb') ----
@@ -368,13 +370,20 @@ class MMDiTGPU(ModuleSurface):
         return self._pos_cache[key]
 
     @torch.no_grad()
-    def velocity_tokens(self, x, t_freq, ctx0, n_live: int, context_see_xt: bool = True, cqkv0=None, tables=None, t_key=None):
+    def velocity_tokens(self, x, t_freq, ctx0, n_live: int, context_see_xt: bool = True, cqkv0=None, tables=None, t_key=None, kmask=None):
         """one model evaluation inside the sampler: returns the FinalLayer tokens [B,256,64].  `t_key`: a hashable name of the
-        timestep t_freq embeds (the same for every sample), see `_step_modulations`."""
+        timestep t_freq embeds (the same for every sample), see `_step_modulations`.  `kmask`: per-sample visibility words over the
+        context rows (`core`); the kernel ignores the bits at and past n_live."""
         mods = self._step_modulations(t_freq, t_key)
         ctx = ctx0[:, :n_live].contiguous() if n_live < ctx0.shape[1] else ctx0
         return self.core(self.embed_image(x), None, ctx if n_live > 0 else None, context_see_xt, cqkv0=cqkv0 if n_live > 0 else None,
-                         tables=tables, mods=mods)
+                         tables=tables, mods=mods, kmask=kmask if n_live > 0 else None)
+
+    @staticmethod
+    def pack_key_mask(mask: torch.Tensor) -> torch.Tensor:
+        """bool [B, K] visibility pattern -> int32 [B, ceil(K / 32)] words for `core(kmask=)` (key j = bit j & 31 of word j >> 5);
+        device ops only, no host synchronisation"""
+        return ops.pack_key_mask(mask)
 
     @torch.no_grad()
     def gather_context(self, ctx0: torch.Tensor, visible: torch.Tensor = None, index: torch.Tensor = None):
@@ -410,15 +419,18 @@ class MMDiTGPU(ModuleSurface):
         exact = self.gemm == "exact"
         t_freq = self._t_freq_exact(t) if exact else ops.timestep_embed(t.to(self.device).float(), self.freqs, 1000.0)
         ctx = self.embed_context(ehs)
-        kvis = None
+        kvis = kmask = None
         if mask is not None:
             m = mask.to(self.device).bool()
-            # the reference's masks are prefixes (arange(K) <= k); anything else is outside the hot path
+            # the reference's own masks are prefixes (arange(K) <= k): the kvis path.  Any other [B, K] pattern (mask * super_mask) goes to the
+            # attention kernel as per-sample bit words
             cnt = m.sum(dim=1)
             if not bool((m == (torch.arange(m.shape[1], device=m.device)[None] < cnt[:, None])).all()):
-                raise NotImplementedError("MMDiTGPU.__call__: `mask` must be a prefix mask (arange(K) <= k, models_ours.py:353); decode other visibility "
-                                          "patterns through SelftokPipeline.decoding(super_mask=)")
-            if exact:
+                if exact:
+                    raise NotImplementedError("MMDiTGPU.__call__: gemm='exact' takes prefix masks only (arange(K) <= k, models_ours.py:353); evaluate other "
+                                              "visibility patterns with gemm='fp32' / 'f16x2'")
+                kmask = self.pack_key_mask(m)
+            elif exact:
                 # gemm='exact' keeps every context key at its position in the reference's key sequence and takes ONE visibility prefix per call (the
                 # sampler's case): a batch-uniform mask is that prefix; a per-sample one would need the per-sample key walk the exact attention does not have
                 if not bool((cnt == cnt[0]).all()):
@@ -428,7 +440,7 @@ class MMDiTGPU(ModuleSurface):
                 ctx = ctx[:, :n_live].contiguous() if n_live > 0 else None
             else:
                 kvis = (cnt - 1).to(torch.int32).contiguous()
-        out = self.core(self.embed_image(x.to(self.device).float()), self.time_embed(t_freq), ctx, see, kvis)
+        out = self.core(self.embed_image(x.to(self.device).float()), self.time_embed(t_freq), ctx, see, kvis, kmask=kmask)
         _, v = ops.unpatchify_cfg_euler(out, C=16, hp=Hh // 2, wp=Ww // 2)
         return v, torch.zeros(B, dtype=torch.bool)
 

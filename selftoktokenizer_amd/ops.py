@@ -523,10 +523,24 @@ def _seg(q, k, v, o):
 ATTN_F16X2 = 1
 
 
-def attention(seg0, seg1, heads, head_dim, kvis=None, seg0_sees_seg1=True, scale=None, mode: int = 0, overflow=None):
+def pack_key_mask(mask: torch.Tensor) -> torch.Tensor:
+    """bool / 0-1 [B, K] -> int32 [B, ceil(K / 32)], the `kmask` words of `attention`: bit j & 31 of word j >> 5 is key j.
+    Device ops only (no host synchronisation: legal before and inside a graph capture)."""
+    B, K = mask.shape
+    W = (K + 31) // 32
+    m = torch.zeros(B, W * 32, dtype=torch.int64, device=mask.device)
+    m[:, :K] = mask != 0
+    words = (m.view(B, W, 32) << torch.arange(32, device=mask.device, dtype=torch.int64)).sum(dim=2)     # 0 .. 2^32 - 1
+    return torch.where(words >= (1 << 31), words - (1 << 32), words).to(torch.int32).contiguous()       # the same 32 bits, as int32
+
+
+def attention(seg0, seg1, heads, head_dim, kvis=None, seg0_sees_seg1=True, scale=None, mode: int = 0, overflow=None,
+              kmask=None, kmask_bs=None):
     """seg = (q, k, v, o) tuples of [B,L,heads*head_dim] views (q and o None: keys/values only; seg None: empty).
     Writes into the `o` views.  kvis: int32 [B] or None.  mode = ATTN_F16X2: f16x2-split matrix products (head_dim 64),
-    `overflow` (int32 [1] device tensor) gets bit 2 if an operand is outside the fp16 range."""
+    `overflow` (int32 [1] device tensor) gets bit 2 if an operand is outside the fp16 range.
+    kmask: int32 / uint32 [B, W] words of a per-sample visibility pattern over the segment-0 keys (`pack_key_mask`; exclusive with
+    kvis; bits past the segment's length are ignored), kmask_bs: words per sample (default: kmask's row stride)."""
     lib = _lib.load()
     d = _lib.AttnDesc()
     ref = seg1 if seg1 is not None else seg0
@@ -545,6 +559,12 @@ def attention(seg0, seg1, heads, head_dim, kvis=None, seg0_sees_seg1=True, scale
     d.mode = int(mode) if head_dim == 64 else 0
     d.overflow = _p(overflow)
     import ctypes
+    if kmask is not None:
+        assert kmask.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and kmask.is_cuda and kmask.dim() == 2
+        assert kmask.shape[0] == d.B and kmask.stride(1) == 1
+        bs = int(kmask.stride(0) if kmask_bs is None else kmask_bs)
+        _lib.check(lib.selftok_attn_kmask_f32(ctypes.byref(d), kmask.data_ptr(), bs, _stream()), "selftok_attn_kmask_f32")
+        return
     _lib.check(lib.selftok_attn_f32(ctypes.byref(d), _stream()), "selftok_attn_f32")
 
 

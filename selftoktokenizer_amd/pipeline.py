@@ -15,7 +15,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, gemm_tune, ops, weights as W
+from . import _lib, gemm_tune, ops, tokens, weights as W
 from .encoder import QformerEncoderGPU, sinusoid_host
 from .mmdit import MMDiTGPU
 from .modsurface import ModuleSurface
@@ -101,14 +101,29 @@ class _Flow(FlowSchedule):
     @torch.no_grad()
     def p_sample_loop(self, dit: MMDiTGPU, noise: torch.Tensor, ehs: torch.Tensor, k_table: np.ndarray,
                       context_see_xt: bool = True, uncond_scale: float = 1.0, max_steps: Optional[int] = None,
-                      trace: Optional[list] = None, prefix_k: Optional[int] = None, super_mask=None, visible=None) -> torch.Tensor:
+                      trace: Optional[list] = None, prefix_k: Optional[int] = None, super_mask=None, visible=None, key_mask=None) -> torch.Tensor:
         """`prefix_k`: the reference loop's `super_mask` (rectified_flow.py:226-227, mask = mask * super_mask) for the prefix mask
         arange(K) < prefix_k -- only the first prefix_k tokens are ever visible (decode from a partial token sequence).
         `super_mask`: the same hook for ANY visibility pattern over the K tokens ([K] bool / 0-1, the same for every sample): the visible
         tokens are gathered once (MMDiTGPU.gather_context) and the step mask is a prefix of that list.  `visible`: the same pattern
         already resolved by `resolve_super_mask` -- what a caller that captures this loop in a hipGraph passes (the resolution reads
-        the mask on the host and uploads an index tensor, neither of which may happen while a stream is capturing)."""
+        the mask on the host and uploads an index tensor, neither of which may happen while a stream is capturing).
+        `key_mask`: a visibility pattern PER SAMPLE, decoded as one batch: `(words, rows)` = (device int32 [B, W] from
+        MMDiTGPU.pack_key_mask, the same masks as a host bool array [B, K]), both made before the loop (and before any capture).  The
+        joint attention takes the words (selftok_attn_kmask_f32) and ignores the bits at and past a step's n_live; the host copy only
+        decides whether a step has any visible key at all."""
         B = noise.shape[0]
+        kwords = any_below = None
+        if key_mask is not None:
+            if visible is not None or super_mask is not None or prefix_k is not None:
+                raise ValueError("key_mask is exclusive with prefix_k / super_mask")
+            if dit.gemm == "exact":
+                raise NotImplementedError("gemm='exact' reproduces the reference's bits for ONE prefix visibility pattern per call; decode per-sample patterns with gemm='fp32' / 'f16x2'")
+            kwords, rows = key_mask
+            rows = np.asarray(rows, dtype=bool)
+            if rows.shape != (B, int(ehs.shape[1])) or tuple(kwords.shape) != (B, (rows.shape[1] + 31) // 32):
+                raise ValueError(f"key_mask: expected words [B, ceil(K/32)] and rows [B, K] = [{B}, {int(ehs.shape[1])}]")
+            any_below = np.concatenate([[False], np.cumsum(rows.any(axis=0)) > 0])     # any_below[n]: some sample has a visible key < n
         x = noise.to(self.device).float().contiguous()
         hp, wp = x.shape[-2] // 2, x.shape[-1] // 2
         ctx0 = dit.embed_context(ehs)                                         # step independent
@@ -130,16 +145,18 @@ class _Flow(FlowSchedule):
                 n_live = min(n_live, int(prefix_k))
             if vis_pos is not None:                                           # visible tokens at positions < n_live: a prefix of the gathered list
                 n_live = int(np.searchsorted(vis_pos, n_live, side="left"))
+            if any_below is not None and not any_below[n_live]:               # no sample sees a key at this step: the n_live = 0 route
+                n_live = 0
             exact = dit.gemm == "exact" and self.t_freq_exact is not None
             tf = (self.t_freq_exact if exact else self.t_freq)[i:i + 1].expand(B, -1).contiguous()
             t_name = float(self.scheduled_t[i])                               # names the embedded timestep (MMDiTGPU._step_modulations)
             if uncond_scale == 1.0:
-                y = dit.velocity_tokens(x, tf, ctx0, n_live, context_see_xt, cqkv0, tables, t_key=("t", t_name))
+                y = dit.velocity_tokens(x, tf, ctx0, n_live, context_see_xt, cqkv0, tables, t_key=("t", t_name), kmask=kwords)
                 yu = None
             else:
                 # CFG branch (rectified_flow.py:280-289): the conditional call omits context_see_xt (-> False) and
                 # the unconditional one sees no context token at all
-                y = dit.velocity_tokens(x, tf, ctx0, n_live, False, cqkv0, tables, t_key=("t", t_name))
+                y = dit.velocity_tokens(x, tf, ctx0, n_live, False, cqkv0, tables, t_key=("t", t_name), kmask=kwords)
                 tfu = (self.t_freq_uncond_exact if exact else self.t_freq_uncond)[i:i + 1].expand(B, -1).contiguous()
                 yu = dit.velocity_tokens(x, tfu, ctx0, 0, False, t_key=("floor", t_name))   # cfg_inference: no context key visible at all
             if self.parameterization == "x0":
@@ -363,12 +380,28 @@ class SelftokPipeline():
         return out
 
     @torch.no_grad()
-    def _sample(self, xt, ehs, max_steps, uncond_scale, use_graph, prefix_k=None, super_mask=None):
+    def _sample(self, xt, ehs, max_steps, uncond_scale, use_graph, prefix_k=None, super_mask=None, mask_batched=False):
         """the 50-step loop, optionally replayed from a hipGraph captured once per (batch, latent size) -- the loop is
-        ~21k kernel launches; at small batch the host cannot issue them as fast as the GPU retires them."""
+        ~21k kernel launches; at small batch the host cannot issue them as fast as the GPU retires them.
+        `mask_batched`: a [B, K] super_mask with differing rows is decoded as ONE batch (per-sample key bit masks in the joint
+        attention) instead of one sampler call per group of equal rows."""
+        key_mask = km_key = None
         if super_mask is not None:
             sm = torch.as_tensor(super_mask).cpu()
-            if sm.dim() == 2 and sm.shape[0] == xt.shape[0] and not bool((sm == sm[:1]).all()):
+            differ = sm.dim() == 2 and sm.shape[0] == xt.shape[0] and not bool((sm == sm[:1]).all())
+            if differ and mask_batched:
+                if self.model.model.gemm == "exact":
+                    raise NotImplementedError("gemm='exact' takes one prefix visibility pattern per call; decode per-sample patterns with gemm='fp32' / 'f16x2'")
+                if prefix_k is not None:
+                    raise ValueError("mask_batched is exclusive with prefix_k")
+                rows = sm.reshape(sm.shape[0], -1).bool().numpy()
+                if rows.shape[1] != self.K:
+                    raise ValueError(f"super_mask has {rows.shape[1]} entries per sample, the tokenizer has K = {self.K} tokens")
+                key_mask = (MMDiTGPU.pack_key_mask(torch.from_numpy(rows).to(self.device)), rows)       # upload + device ops: before any capture
+                import hashlib
+                km_key = hashlib.sha256(rows.tobytes()).hexdigest()
+                super_mask = None
+            elif differ:
                 # a visibility pattern PER SAMPLE (the reference's `mask * super_mask` with a [B, K] tensor, rectified_flow.py:226-227):
                 # samples are independent, so the batch is decoded in groups of equal pattern (a group's context is gathered once)
                 rows = sm.reshape(sm.shape[0], -1).bool().numpy()
@@ -382,16 +415,16 @@ class SelftokPipeline():
                 return out
         if not use_graph:
             return self.flow.p_sample_loop(self.model.model, xt, ehs, self.k_table, context_see_xt=True,
-                                           uncond_scale=uncond_scale, max_steps=max_steps, prefix_k=prefix_k, super_mask=super_mask)
+                                           uncond_scale=uncond_scale, max_steps=max_steps, prefix_k=prefix_k, super_mask=super_mask, key_mask=key_mask)
         visible = None if super_mask is None else self.flow.resolve_super_mask(super_mask, self.K)     # host read + upload: before the capture
         sm_key = None if visible is None else visible[1].tobytes()
-        key = (tuple(xt.shape), tuple(ehs.shape), max_steps, float(uncond_scale), self.model.model.gemm, self.model.model.PRESPLIT, self.model.model.SPLITK, prefix_k, sm_key)
+        key = (tuple(xt.shape), tuple(ehs.shape), max_steps, float(uncond_scale), self.model.model.gemm, self.model.model.PRESPLIT, self.model.model.SPLITK, prefix_k, sm_key, km_key)
         if key not in self._graphs:
             s_noise = torch.empty(xt.shape, dtype=torch.float32, device=self.device)
             s_ehs = torch.empty_like(ehs)
             s_noise.copy_(xt); s_ehs.copy_(ehs)
             run = lambda: self.flow.p_sample_loop(self.model.model, s_noise, s_ehs, self.k_table, context_see_xt=True,
-                                                  uncond_scale=uncond_scale, max_steps=max_steps, prefix_k=prefix_k, visible=visible)
+                                                  uncond_scale=uncond_scale, max_steps=max_steps, prefix_k=prefix_k, visible=visible, key_mask=key_mask)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):       # warm-up outside capture (hipBLASLt / allocator warm)
@@ -416,16 +449,37 @@ class SelftokPipeline():
     @torch.no_grad()
     def decoding(self, idx, device=None, noise: Optional[torch.Tensor] = None, return_latent: bool = False,
                  max_steps: Optional[int] = None, uncond_scale: float = 1.0, use_graph: bool = False,
-                 prefix_k: Optional[int] = None, super_mask=None):
+                 prefix_k: Optional[int] = None, super_mask=None, ar_partial=None, mask_batched: bool = False):
         """idx: np.ndarray int64 [B,K] -> bf16 [B,3,H,W] in [0,1] (reference :227-294).  `noise` (extension) replaces the
         `torch.randn` draw from the global CPU generator (:264); `uncond_scale` exposes the dormant CFG branch
-        (p_sample_loop's argument of that name).  `prefix_k` (extension): decode from the first prefix_k tokens only -- the
-        reference loop's `super_mask` hook with a prefix mask (rectified_flow.py:226-227; README.md:241: an AR model emits the
-        sequence in reverse order, `tokens.from_ar_order` restores it and `tokens.pad_prefix` pads a partial one to [B,K]).
-        `super_mask` (extension): the same hook with any visibility pattern over the K tokens ([K] bool / 0-1 array)."""
+        (p_sample_loop's argument of that name).
+        `ar_partial` (extension): THE route for a partial sequence of an AR model.  An AR model emits the tokens in reverse
+        (README.md:241): tokenizer index K - 1 first, index 0 last, so its first m tokens are the positions K - m .. K - 1.
+        m is an int or one value per sample (0 <= m_b <= K); `tokens.pad_ar_partial` builds idx from what the model emitted.  Sugar for
+        super_mask = `tokens.suffix_mask(K, m)`: equal m_b run the uniform route below, differing m_b run ONE batched pass with
+        per-sample key masks in the joint attention.  Exclusive with prefix_k / super_mask.
+        `prefix_k` (extension): the reference loop's `super_mask` hook (rectified_flow.py:226-227) with the mask arange(K) < prefix_k:
+        tokens 0 .. prefix_k - 1, the FINE end of the sequence (`tokens.pad_prefix`).  It is not the AR partial route.
+        `super_mask` (extension): the same hook with any visibility pattern over the K tokens ([K] bool / 0-1 array, or [B, K]: one
+        pattern per sample, decoded in groups of equal pattern -- or, with `mask_batched=True`, as one batch)."""
         self._say("Begin decoding.")
         if prefix_k is not None and not (0 <= int(prefix_k) <= self.K):
             raise ValueError(f"prefix_k must be in [0, {self.K}]")
+        if ar_partial is not None:
+            if prefix_k is not None or super_mask is not None:
+                raise ValueError("ar_partial is exclusive with prefix_k / super_mask")
+            B_ = int(np.asarray(idx.cpu() if torch.is_tensor(idx) else idx).shape[0])
+            m = np.asarray(ar_partial, dtype=np.int64).reshape(-1)
+            m = np.repeat(m, B_) if m.size == 1 else m
+            if m.size != B_:
+                raise ValueError(f"ar_partial: expected an int or {B_} values, got {m.size}")
+            if m.min() < 0 or m.max() > self.K:
+                raise ValueError(f"ar_partial must be in [0, {self.K}]")
+            sm = tokens.suffix_mask(self.K, m)
+            if bool((m == m[0]).all()):
+                super_mask = sm[0]                                           # the existing uniform route (gathered context)
+            else:
+                super_mask, mask_batched = sm, True
         outs_q = self._codes(idx)
         B = outs_q.shape[0]
         # t_mapped = timestep_map[0] -> k = K-1 -> enc_mask all true -> encoder_hidden_states = outs_q (:243-252)
@@ -435,7 +489,7 @@ class SelftokPipeline():
         xt = noise if noise is not None else torch.randn(B, 16, latent_dim, latent_dim)
         self._tune_linears(B * (2 if uncond_scale != 1.0 else 1), self.k_table, (latent_dim // 2) ** 2)
         with self._tunable_scope():
-            pred_x0 = self._checked(lambda: self._sample(xt, ehs, max_steps, uncond_scale, use_graph, prefix_k, super_mask))
+            pred_x0 = self._checked(lambda: self._sample(xt, ehs, max_steps, uncond_scale, use_graph, prefix_k, super_mask, mask_batched))
         recons = self._to_pixels(pred_x0)
         self._say('End decoding.')
         return (recons, pred_x0) if return_latent else recons

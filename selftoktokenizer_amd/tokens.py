@@ -3,8 +3,11 @@
 The reference hands tokens around as `np.save` of an int64 `[B,K]` array (test.py:38-39) -- 8 bytes per 15-bit id.
 Ids are < 32768 = 2^15, so they also fit uint16 (4x smaller) or a dense 15-bit stream (4.27x smaller); both are
 lossless and round-trip to the reference's int64 layout.  `reverse_for_ar` implements the README's note for AR
-training ("decode the sequence reversely", README.md:241): tokens are ordered from the most detailed (index 0,
-visible only at small t) to the coarsest, an AR model consumes them in reverse.
+training ("decode the sequence reversely", README.md:241).  The sampler's step mask is `arange(K) <= k(t)` with k falling
+from K - 1 (models_ours.py:345-353): index 0 is visible at EVERY step, index K - 1 only at the first ones (large t).  An AR
+model emits index K - 1 first and index 0 last, so the first m tokens it has emitted are the tokenizer positions K - m .. K - 1,
+a SUFFIX: `pad_ar_partial` / `suffix_mask` place them, `SelftokPipeline.decoding(ar_partial=m)` decodes from them.
+`pad_prefix` / `prefix_mask` serve the reference's other hook, `arange(K) < k` (decoding(prefix_k=)): NOT the AR partial route.
 """
 from __future__ import annotations
 
@@ -72,6 +75,36 @@ def pad_prefix(prefix, K: int, fill: int = 0):
     out = np.full((t.shape[0], K), fill, dtype=np.int64)
     out[:, : t.shape[1]] = t
     return out, int(t.shape[1])
+
+
+def pad_ar_partial(ar_tokens, K: int, fill: int = 0):
+    """what an AR model has emitted so far, in the order it emitted it (coarse first) -> (int64 [B,K] ids in tokenizer order, int64 [B] m).
+    `ar_tokens`: [B,m], or a list of B 1-D sequences of different lengths m_b <= K.  Token i of sample b lands at tokenizer position
+    K - 1 - i; every other position holds `fill` (never read: `suffix_mask(K, m)` hides it).  The arguments of
+    `SelftokPipeline.decoding(idx, ar_partial=m)`."""
+    if isinstance(ar_tokens, np.ndarray) and ar_tokens.ndim == 2:
+        rows = list(ar_tokens)
+    else:
+        rows = [np.asarray(r) for r in ar_tokens]
+    out = np.full((len(rows), K), fill, dtype=np.int64)
+    m = np.zeros(len(rows), dtype=np.int64)
+    for b, r in enumerate(rows):
+        r = np.asarray(r)
+        if r.ndim != 1 or r.shape[0] > K:
+            raise ValueError(f"sample {b}: expected a 1-D sequence of at most K = {K} tokens, got shape {r.shape}")
+        if r.size and not np.issubdtype(r.dtype, np.integer):
+            raise TypeError(f"token ids must be integers, got {r.dtype}")
+        m[b] = r.shape[0]
+        out[b, K - r.shape[0]:] = r[::-1]
+    return out, m
+
+
+def suffix_mask(K: int, m) -> np.ndarray:
+    """bool [B,K]: arange(K) >= K - m[b], the positions the first m[b] tokens of an AR model occupy (`pad_ar_partial`)"""
+    m = np.asarray(m, dtype=np.int64).reshape(-1, 1)
+    if m.size and (m.min() < 0 or m.max() > K):
+        raise ValueError(f"m must be in [0, {K}]")
+    return np.arange(K)[None, :] >= K - m
 
 
 def prefix_mask(K: int, k) -> np.ndarray:

@@ -918,6 +918,41 @@ def stage_sampler_options():
     np.savez_compressed(os.path.join(GOLD, "sampler_options_b1.npz"), **out)
 
 
+def stage_ar_partial():
+    """partial AR sequences with a different progress per sample, from the reference's own RectifiedFlow.sample_one_step on the real
+    MMDiT: B = 4, steps 0 and 1, context_see_xt=True, cfg_scale = 1.0, mask = get_encoder_mask(x, k) * suffix_mask with
+    m = (512, 301, 37, 1) emitted tokens (an AR model emits tokenizer index K - 1 first: its first m tokens are positions K - m .. K - 1).
+    m = 1 leaves its sample with a visible token only while k = K - 1; the per-step k and visible counts are recorded."""
+    cfg, model, sd = tokenizer(CFG_256)
+    H.install()
+    from mimogpt.models.selftok.sd3.rectified_flow import RectifiedFlow
+    from mimogpt.models.selftok.diti_utils import DiTi_cont
+    B, K = 4, 512
+    diti = DiTi_cont(1000, K, cfg.tokenizer.params.stages, cfg.tokenizer.params.k_per_stage)
+    ids = torch.from_numpy(synth.synthetic_token_ids(B, first_index=40))
+    with torch.no_grad():
+        codes = model.encoder.quantizer.get_output_from_indices(ids)
+        ehs = model.encoder.final_layer_norm3(codes.reshape(B, -1, 16))
+    x = synth.synthetic_noise(B, first_index=40)
+    m = torch.tensor([512, 301, 37, 1])
+    suf = torch.arange(K)[None, :] >= (K - m)[:, None]
+    flow = RectifiedFlow(50, 1.0, None, val_schedule="uniform", shift=1.0, schedule="log_norm", parameterization="velocity", m=0.0, s=1.0,
+                         force_recon=False, is_eval=True)
+    out = {"ids": ids.numpy(), "m": m.numpy(), "k": np.zeros(2, np.int64), "visible": np.zeros((2, B), np.int64)}
+    xr = x.clone()
+    for i in (0, 1):
+        t = torch.tensor([flow.scheduled_t[i]] * B)
+        k = diti.to_indices(torch.tensor([flow.timestep_map[i]] * B).long())
+        mask = model.encoder.get_encoder_mask(x, k) * suf
+        kw = dict(encoder_hidden_states=ehs, mask=mask, context_see_xt=True)
+        with torch.no_grad():
+            xr, _ = flow.sample_one_step(model.model, xr, t, index=i, model_kwargs=kw, cfg_scale=1.0)
+        out["k"][i] = int(k[0]); out["visible"][i] = mask.reshape(B, -1).sum(dim=1).numpy()
+        out[f"after_{i + 1}"] = xr.numpy()
+        report(f"ar_partial_step{i}", k=int(k[0]), visible=[int(v) for v in out["visible"][i]], absmax=float(xr.abs().max()), finite=bool(torch.isfinite(xr).all()))
+    np.savez_compressed(os.path.join(GOLD, "ar_partial_b4.npz"), **out)
+
+
 def stage_k1024():
     """BASELINE configs[2]: the reference's own ImageTokenizer built with k = 1024 (query_tokens / context_pos_embed grow, stage
     split ASSUMED 384,368,144,96,32 -- the reference ships no 1024 config): encoder features + ids, and one MMDiT.forward."""
@@ -1128,7 +1163,7 @@ def stage_rmsnorm_rotary():
     report("rmsnorm_rotary", arrays=sorted(out), rms_absmax=float(np.abs(out["rms_affine"]).max()), rot_absmax=float(np.abs(out["rot_full"]).max()))
 
 
-STAGES = dict(encoder_prenorm=stage_encoder_prenorm, pipeline64=stage_pipeline64, k1024_pipe16=stage_k1024_pipe16, renderer16=stage_renderer16, res128=lambda: stage_res(128), res320=lambda: stage_res(320), k1024_16=stage_k1024_16, cfg16=stage_cfg16, dit4=stage_dit4, config=stage_config, decode16=stage_decode16, encode64=stage_encode64, vq_entropy=stage_vq_entropy, rmsnorm_rotary=stage_rmsnorm_rotary, sampler_options=stage_sampler_options, keys=stage_keys, vq=stage_vq, schedule=stage_schedule, encoder=stage_encoder, dit=stage_dit,
+STAGES = dict(encoder_prenorm=stage_encoder_prenorm, pipeline64=stage_pipeline64, k1024_pipe16=stage_k1024_pipe16, renderer16=stage_renderer16, res128=lambda: stage_res(128), res320=lambda: stage_res(320), k1024_16=stage_k1024_16, cfg16=stage_cfg16, dit4=stage_dit4, config=stage_config, decode16=stage_decode16, encode64=stage_encode64, vq_entropy=stage_vq_entropy, rmsnorm_rotary=stage_rmsnorm_rotary, sampler_options=stage_sampler_options, ar_partial=stage_ar_partial, keys=stage_keys, vq=stage_vq, schedule=stage_schedule, encoder=stage_encoder, dit=stage_dit,
               vae=stage_vae, pipeline=stage_pipeline, pipeline16=stage_pipeline16, renderer=stage_renderer, cfg=stage_cfg, k1024=stage_k1024, vqtrain=stage_vqtrain)
 
 if __name__ == "__main__":
