@@ -23,6 +23,21 @@ extern "C" {
  * (seg[1], seg0_sees_seg1, strides, mode, overflow, o_blk) means what it means in selftok_attn_f32. */
 int selftok_attn_kmask_f32(const selftok_attn_desc* desc, const unsigned* kmask, long kmask_bs, hipStream_t stream);
 
+/* ---- exact-order attention with a per-sample key bit mask ----------------------------------------
+ * The two exact-order attention entries of selftok_hip.h (ATen's fp32 CPU flash kernel, bit for bit; unfused and fused) with ANY
+ * visibility pattern over the first segment's Tk1 key slots: the boolean mask the reference hands to SDPA is the same ATen code
+ * path for a prefix and for every other pattern.  The bit layout is selftok_attn_kmask_f32's: slot j of sample b is visible iff
+ * j < valid1 and bit (j & 31) of word kmask[b * kmask_bs + (j >> 5)] is set (`mask * super_mask`: the step prefix and the pattern
+ * combine); kmask_bs == 0: one pattern for the whole batch, else kmask_bs >= ceil(Tk1 / 32).  Tk1 <= 2048.  The second segment is
+ * always visible.  A masked key keeps its slot in the 512-key blocks, adds an exact zero and is never read into the arithmetic
+ * (NaN and Inf included): prefix bits give the bits of the entries without a mask.  A sample without any visible key is legal
+ * here: the fused entry does not write its rows, the unfused one writes zeros -- pass a zero-filled `out` when that can happen
+ * (ATen yields NaN there).  Every other argument and constraint is that of the entry without a mask. */
+int selftok_ex_attention_kmask_f32(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
+                                   long kvs2, int Tk2, float* out, void* workspace, int B, int H, int Tq, int D, const unsigned* kmask, long kmask_bs, hipStream_t stream);
+int selftok_ex_attention_kmask_fused_f32(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
+                                         long kvs2, int Tk2, float* out, int B, int H, int Tq, int D, const unsigned* kmask, long kmask_bs, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

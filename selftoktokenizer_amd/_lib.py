@@ -83,6 +83,8 @@ SIGNATURES = {
 # entries of include/selftok_hip_ext.h: exported by libselftok_hip.so only (no CPU twin yet)
 EXT_SIGNATURES = {
     "selftok_attn_kmask_f32": (_i, [_vp, _vp, _l, _vp]),
+    "selftok_ex_attention_kmask_f32": (_i, [_vp, _l, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _l, _i, _vp, _vp, _i, _i, _i, _i, _vp, _l, _vp]),
+    "selftok_ex_attention_kmask_fused_f32": (_i, [_vp, _l, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _l, _i, _vp, _i, _i, _i, _i, _vp, _l, _vp]),
 }
 
 

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "exact_math.h"
 #include "selftok_hip.h"
+#include "selftok_hip_ext.h"
 
 namespace selftok {
 
@@ -722,7 +723,12 @@ __global__ __launch_bounds__(512) void xe_lnw_kernel(const float* x, long ldx, f
 // rescale [nb - 1][rows] = expf(max before block j - max after block j) for j >= 1; rowscale [rows] = 1 / sum.  16 threads per row:
 // lane = key mod 16 sums its probabilities sequentially, then the 8 / 4 / 2 / 1 fold of vec_reduce_all.  Tk % 16 == 0.
 // keys mlo .. mhi-1 are masked out (never computed, never read): score -inf, probability 0 written.
-__global__ __launch_bounds__(256) void xe_softmax_kernel(float* __restrict__ s, float* __restrict__ rescale, float* __restrict__ rowscale, long rows, int Tk, int mlo, int mhi)
+// KMASK: a key below mlo is masked too unless its bit is set in the row's sample's words (bit key & 31 of kmask[sample * kmask_bs + (key >> 5)], sample = row /
+// rows_per_sample): the score GEMM may have computed such a column (from an invisible key: any bits, NaN included), this pass does not read it.  A row without any
+// visible key gets rowscale 0 (its probabilities are zeros: the P V product writes zeros, where ATen's 0 * (1 / 0) is NaN).
+template <bool KMASK>
+__global__ __launch_bounds__(256) void xe_softmax_kernel(float* __restrict__ s, float* __restrict__ rescale, float* __restrict__ rowscale, long rows, int Tk, int mlo, int mhi,
+                                                         const unsigned* __restrict__ kmask, long kmask_bs, long rows_per_sample)
 {
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long row = gid >> 4;
@@ -731,6 +737,8 @@ __global__ __launch_bounds__(256) void xe_softmax_kernel(float* __restrict__ s, 
     float* sr = s + (size_t)row * Tk;
     float m_old = -__builtin_inff(), sum_old = 0.f;
     int jb = 0;
+    const unsigned* kw = nullptr;
+    if constexpr (KMASK) kw = kmask + (size_t)(row / rows_per_sample) * kmask_bs;
     for (int n0 = 0; n0 < Tk; n0 += 512, ++jb) {
         const int nb = min(512, Tk - n0), cnt = nb >> 4;
         float v[32];
@@ -738,7 +746,9 @@ __global__ __launch_bounds__(256) void xe_softmax_kernel(float* __restrict__ s, 
 #pragma unroll
         for (int k = 0; k < 32; ++k) if (k < cnt) {
             const int key = n0 + 16 * k + l;
-            v[k] = (key >= mlo && key < mhi) ? -__builtin_inff() : sr[key];
+            bool masked = key >= mlo && key < mhi;
+            if constexpr (KMASK) masked = masked || (key < mlo && ((kw[key >> 5] >> (key & 31)) & 1u) == 0);
+            v[k] = masked ? -__builtin_inff() : sr[key];
             bm = fmaxf(bm, v[k]);
         }
 #pragma unroll
@@ -760,19 +770,26 @@ __global__ __launch_bounds__(256) void xe_softmax_kernel(float* __restrict__ s, 
         m_old = m_new;
         if (jb > 0 && l == 0) rescale[(size_t)(jb - 1) * rows + row] = exp_tmp;
     }
-    if (l == 0) rowscale[row] = 1.0f / sum_old;
+    if (l == 0) rowscale[row] = (KMASK && sum_old == 0.f) ? 0.f : 1.0f / sum_old;
 }
 
 // v [B][T][*] (row stride vs, head h at column h D) -> vt [B][H][D][Tk] at key offset t_off: the P V product reads V as [d][key]
 // T = key slots of this segment, `valid` of them present (rows valid .. T-1 are masked keys: zeros, never read), `rows` = rows per batch in v
-__global__ void xe_transpose_v_kernel(const float* __restrict__ v, long vs, float* __restrict__ vt, int T, int valid, int rows, int H, int D, int Tk, int t_off)
+// KMASK: a row below `valid` whose bit is clear in its sample's words is a masked key as well
+template <bool KMASK>
+__global__ void xe_transpose_v_kernel(const float* __restrict__ v, long vs, float* __restrict__ vt, int T, int valid, int rows, int H, int D, int Tk, int t_off,
+                                      const unsigned* __restrict__ kmask, long kmask_bs)
 {
     __shared__ float tile[32][33];
     const int z = blockIdx.z, b = z / H, h = z - b * H;
     const int t0 = blockIdx.x * 32, d0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int r = ty; r < 32; r += 8)
-        if (t0 + r < T && d0 + tx < D) tile[r][tx] = (t0 + r < valid) ? v[((size_t)b * rows + t0 + r) * vs + h * D + d0 + tx] : 0.0f;
+        if (t0 + r < T && d0 + tx < D) {
+            bool on = t0 + r < valid;
+            if constexpr (KMASK) on = on && ((kmask[(size_t)b * kmask_bs + ((t0 + r) >> 5)] >> ((t0 + r) & 31)) & 1u) != 0;
+            tile[r][tx] = on ? v[((size_t)b * rows + t0 + r) * vs + h * D + d0 + tx] : 0.0f;
+        }
     __syncthreads();
     for (int r = ty; r < 32; r += 8)
         if (d0 + r < D && t0 + tx < T) vt[((size_t)z * D + d0 + r) * Tk + t_off + t0 + tx] = tile[tx][r];
@@ -805,6 +822,7 @@ struct XfArgs {
     float* out;
     int B, H, Tq, qtiles;
     float scale;
+    const unsigned* kmask; long kmask_bs;      // KMASK instantiation: visibility words of the segment-1 slots, words per sample (0: one pattern for the batch)
 };
 
 __device__ __forceinline__ void xf_dma16(const void* base, unsigned voff, unsigned lds)
@@ -812,8 +830,24 @@ __device__ __forceinline__ void xf_dma16(const void* base, unsigned voff, unsign
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds) : "memory", "m0");
 }
 
+// a global pointer whose target no kernel of the launch writes, read as CONSTANT memory: a uniform address is then a scalar-cache load whatever else the kernel
+// does to memory (the LDS-DMA statements clobber "memory", which would otherwise turn the mask words into vector loads)
+#define XE_CONSTANT __attribute__((address_space(4)))
+__device__ __forceinline__ const XE_CONSTANT unsigned* xe_constant(const unsigned* p)
+{
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    return (const XE_CONSTANT unsigned*)p;
+#pragma clang diagnostic pop
+}
+
 struct XfStep { int jb, sweep, t; };          // kv block, sweep (1: maximum, 2: probabilities + P V), staged key tile (64 slots) -- all uniform
 
+// KMASK = true: the visible segment-1 slots are the set bits of the sample's words below valid1 instead of the prefix 0 .. valid1 - 1 (any pattern: the reference's
+// `mask * super_mask`).  LDS is full, so the two words of a 64-slot tile are read per tile through the scalar cache (uniform: one workgroup is one sample).  A tile
+// without a visible slot is skipped, a 32-slot half with an empty word likewise; a mixed half sets its masked scores to -inf before the maximum and exp_u20, and
+// the staging of a masked slot fetches a visible row of the same tile, so an invisible key's K / V (NaN, Inf) never reaches an MFMA.
+template <bool KMASK>
 __global__ __launch_bounds__(256, 2) void xe_fattn_kernel(XfArgs a)
 {
     __shared__ __attribute__((aligned(1024))) float s_k[2][64 * 64];
@@ -847,6 +881,16 @@ __global__ __launch_bounds__(256, 2) void xe_fattn_kernel(XfArgs a)
     const unsigned lds_k = (unsigned)(size_t)(__attribute__((address_space(3))) float*)&s_k[0][0];
     const unsigned lds_v = (unsigned)(size_t)(__attribute__((address_space(3))) float*)&s_v[0][0];
     const int kr = lane >> 4, pos = lane & 15;                 // row inside a piece, 16-byte position inside the 256-byte row
+    // KMASK: the visible slots of key tile t, halves e0 (slots 0..31) and e1 (32..63); segment 2: all; segment 1: the sample's words cut at valid1.  Uniform.
+    auto words = [&](int t, unsigned& e0, unsigned& e1) {
+        const int s0 = t * 64;
+        if (s0 >= a.Tk1) { e0 = ~0u; e1 = ~0u; return; }
+        const XE_CONSTANT unsigned* w = xe_constant(a.kmask) + (size_t)b * a.kmask_bs + 2 * t;
+        const int n = a.valid1 - s0;
+        const unsigned w0 = w[0], w1 = w[1];
+        e0 = n >= 32 ? w0 : n > 0 ? (w0 & ((1u << n) - 1u)) : 0u;
+        e1 = n >= 64 ? w1 : n > 32 ? (w1 & ((1u << (n - 32)) - 1u)) : 0u;
+    };
     auto stage = [&](const XfStep& st, int buf) {
         const int slot0 = st.t * 64;
         const bool seg2 = slot0 >= a.Tk1;
@@ -857,15 +901,30 @@ __global__ __launch_bounds__(256, 2) void xe_fattn_kernel(XfArgs a)
         const char* kb = reinterpret_cast<const char*>(kp + (size_t)b * rows * rs + hd * 64);
         const char* vb = reinterpret_cast<const char*>(vp + (size_t)b * rows * rs + hd * 64);
         const unsigned rs4 = (unsigned)rs * 4u;
+        unsigned e0 = 0, e1 = 0;
+        int fv = 0;                                            // KMASK: a visible row of this tile (advance() returns tiles that have one)
+        if constexpr (KMASK) { words(st.t, e0, e1); fv = e0 ? __builtin_ctz(e0) : 32 + __builtin_ctz(e1); }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int p = wave + 4 * u, row = 4 * p + kr;      // tile row 0..63
-            const int src = min(key0 + row, nvis - 1);         // ragged tile: rows past the visible prefix fetch the last visible key (masked to -inf / probability 0 below)
+            int src;
+            if constexpr (KMASK) src = key0 + ((((row < 32 ? e0 : e1) >> (row & 31)) & 1u) ? row : fv);      // a masked slot fetches a visible row (masked to -inf / probability 0 below)
+            else src = min(key0 + row, nvis - 1);              // ragged tile: rows past the visible prefix fetch the last visible key (masked to -inf / probability 0 below)
             xf_dma16(kb, (unsigned)src * rs4 + (unsigned)((pos ^ (row & 15)) << 4), lds_k + buf * 16384 + p * 1024);
             if (st.sweep == 2) xf_dma16(vb, (unsigned)src * rs4 + (unsigned)(pos << 4), lds_v + buf * 16384 + p * 1024);
         }
     };
-    auto visible = [&](int t) { const int s0 = t * 64; return s0 >= a.Tk1 || s0 < a.valid1; };
+    auto visible = [&](int t) {
+        const int s0 = t * 64;
+        if constexpr (KMASK) {
+            if (s0 >= a.Tk1) return true;
+            if (s0 >= a.valid1) return false;
+            unsigned e0, e1;
+            words(t, e0, e1);
+            return (e0 | e1) != 0u;
+        }
+        return s0 >= a.Tk1 || s0 < a.valid1;
+    };
     auto advance = [&](XfStep st) {                             // successor of a step; jb == nblk: done
         for (;;) {
             ++st.t;
@@ -904,11 +963,18 @@ __global__ __launch_bounds__(256, 2) void xe_fattn_kernel(XfArgs a)
             sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, qf[2 * c + 1], sacc, 0, 0, 0);
         }
     };
-    auto finish_scores = [&](int slot0, f32x16& sacc) {         // * 1/sqrt(d); keys past the visible prefix of a ragged half: -inf
+    auto finish_scores = [&](int slot0, unsigned e, f32x16& sacc) {         // * 1/sqrt(d); keys past the visible prefix of a ragged half (KMASK: without their bit in e): -inf
         const int nvis = slot0 >= a.Tk1 ? 32 : a.valid1 - slot0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sacc[r] = sacc[r] * a.scale;
-        if (nvis < 32) {
+        if constexpr (KMASK) {
+            if (e != ~0u) {
+                const unsigned eh = e >> (4 * hh);
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if ((eh & (1u << ((r & 3) + 8 * (r >> 2)))) == 0u) sacc[r] = -__builtin_inff();
+            }
+        } else if (nvis < 32) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if ((r & 3) + 8 * (r >> 2) + 4 * hh >= nvis) sacc[r] = -__builtin_inff();
@@ -921,7 +987,7 @@ __global__ __launch_bounds__(256, 2) void xe_fattn_kernel(XfArgs a)
 
     XfStep cur{0, 1, -1};
     cur = advance(cur);
-    if (cur.jb >= nblk) return;                                  // (the launcher refuses calls without a visible key)
+    if (cur.jb >= nblk) return;                                  // no visible key (the prefix launcher refuses such calls; KMASK: this sample's rows are not written)
     stage(cur, 0);
     for (int s = 0; cur.jb < nblk; ++s) {
         const XfStep nxt = advance(cur);
@@ -936,14 +1002,18 @@ __global__ __launch_bounds__(256, 2) void xe_fattn_kernel(XfArgs a)
             const int ch = 2 * cur.jb + ((blen == 512 && slot_in_blk >= 256) ? 1 : 0);
             if (ch != chain) { fold_chain(); chain = ch; }
         }
+        unsigned ce0 = ~0u, ce1 = ~0u;
+        if constexpr (KMASK) words(cur.t, ce0, ce1);
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int slot0 = cur.t * 64 + 32 * sub;
-            if (slot0 < a.Tk1 && slot0 >= a.valid1) continue;    // a fully masked half (uniform)
+            const unsigned e = sub ? ce1 : ce0;
+            if constexpr (KMASK) { if (e == 0u) continue; }      // a half without a visible key (uniform)
+            else if (slot0 < a.Tk1 && slot0 >= a.valid1) continue;    // a fully masked half (uniform)
             if (cur.sweep == 2 && !block_live) continue;
             f32x16 sacc;
             scores(buf, sub, sacc);
-            finish_scores(slot0, sacc);
+            finish_scores(slot0, e, sacc);
             if (cur.sweep == 1) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) lane_max = fmaxf(lane_max, sacc[r]);
@@ -1093,17 +1163,21 @@ size_t selftok_ex_attention_workspace_bytes(int B, int H, int Tq, int Tk, int D)
     return rows * Tk * 4 + (size_t)B * H * D * Tk * 4 + rows * 4 * (size_t)(nb > 1 ? nb - 1 : 1) + rows * 4;
 }
 
-/* q [B][Tq][..] row stride qs; k1 / v1 [B][rows1][..] row stride kvs1 holding the first valid1 of the segment's Tk1 key slots (valid1 == rows1 == Tk1: no
- * mask); optional second key / value segment k2 / v2 [B][Tk2][..] row stride kvs2 (`torch.cat([k, query_k], dim=2)`); head h at column h D of every row;
- * out [B][Tq][H D] contiguous. */
-int selftok_ex_attention_f32(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
-                             long kvs2, int Tk2, float* out, void* workspace, int B, int H, int Tq, int D, hipStream_t stream)
+}  // extern "C"
+
+// kmask == nullptr: the prefix entry.  With words, a call (or a sample) without a visible key is legal: its rows come out as zeros.
+static int ex_attention_unfused(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
+                                long kvs2, int Tk2, float* out, void* workspace, int B, int H, int Tq, int D, const unsigned* kmask, long kmask_bs, hipStream_t stream)
 {
     if (B == 0) return SELFTOK_OK;
     const int Tk = Tk1 + Tk2;
     if (!q || !out || !workspace || B < 0 || H <= 0 || Tq <= 0 || Tk1 <= 0 || Tk2 < 0 || valid1 < 0 || valid1 > Tk1 || rows1 < valid1 || (valid1 > 0 && (!k1 || !v1)) ||
-        (Tk2 > 0 && (!k2 || !v2)) || D % 16 || D <= 0 || D > 128 || Tk1 % 16 || Tk2 % 16 || qs % 4 || kvs1 % 4 || kvs2 % 4 || (valid1 == 0 && Tk2 == 0)) {
+        (Tk2 > 0 && (!k2 || !v2)) || D % 16 || D <= 0 || D > 128 || Tk1 % 16 || Tk2 % 16 || qs % 4 || kvs1 % 4 || kvs2 % 4 || (!kmask && valid1 == 0 && Tk2 == 0)) {
         set_last_error("ex_attention: need head_dim % 16 == 0 (<= 128), key slot counts % 16 == 0, 16-byte aligned rows, 0 <= valid1 <= Tk1 <= ..., at least one visible key");
+        return SELFTOK_EINVAL;
+    }
+    if (kmask && (Tk1 > 2048 || (kmask_bs != 0 && kmask_bs < (Tk1 + 31) / 32))) {
+        set_last_error("ex_attention_kmask: need Tk1 <= 2048 and kmask_bs == 0 (one pattern) or >= ceil(Tk1 / 32)");
         return SELFTOK_EINVAL;
     }
     const int Z = B * H;
@@ -1125,13 +1199,21 @@ int selftok_ex_attention_f32(const float* q, long qs, const float* k1, const flo
         int rc = launch_xe_gemm(g, Z, stream);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(xe_softmax_kernel, dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, stream, s, rescale, rowscale, (long)rows, Tk, valid1, Tk1);
+    if (kmask)
+        hipLaunchKernelGGL(xe_softmax_kernel<true>, dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, stream, s, rescale, rowscale, (long)rows, Tk, valid1, Tk1, kmask, kmask_bs,
+                           (long)H * Tq);
+    else
+        hipLaunchKernelGGL(xe_softmax_kernel<false>, dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, stream, s, rescale, rowscale, (long)rows, Tk, valid1, Tk1,
+                           (const unsigned*)nullptr, 0L, 1L);
     int rc = check_launch("xe_softmax_kernel");
     if (rc) return rc;
     for (int seg = 0; seg < (Tk2 > 0 ? 2 : 1); ++seg) {
         const int T = seg ? Tk2 : Tk1;
-        hipLaunchKernelGGL(xe_transpose_v_kernel, dim3((T + 31) / 32, (D + 31) / 32, Z), dim3(256), 0, stream, seg ? v2 : v1, seg ? kvs2 : kvs1, vt, T, seg ? Tk2 : valid1,
-                           seg ? Tk2 : rows1, H, D, Tk, seg ? Tk1 : 0);
+        if (kmask && seg == 0)
+            hipLaunchKernelGGL(xe_transpose_v_kernel<true>, dim3((T + 31) / 32, (D + 31) / 32, Z), dim3(256), 0, stream, v1, kvs1, vt, T, valid1, rows1, H, D, Tk, 0, kmask, kmask_bs);
+        else
+            hipLaunchKernelGGL(xe_transpose_v_kernel<false>, dim3((T + 31) / 32, (D + 31) / 32, Z), dim3(256), 0, stream, seg ? v2 : v1, seg ? kvs2 : kvs1, vt, T, seg ? Tk2 : valid1,
+                               seg ? Tk2 : rows1, H, D, Tk, seg ? Tk1 : 0, (const unsigned*)nullptr, 0L);
         rc = check_launch("xe_transpose_v_kernel");
         if (rc) return rc;
     }
@@ -1152,6 +1234,28 @@ int selftok_ex_attention_f32(const float* q, long qs, const float* k1, const flo
     return launch_xe_gemm(g, Z, stream);
 }
 
+static int ex_attention_fused(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
+                              long kvs2, int Tk2, float* out, int B, int H, int Tq, int D, const unsigned* kmask, long kmask_bs, hipStream_t stream);
+
+extern "C" {
+
+/* q [B][Tq][..] row stride qs; k1 / v1 [B][rows1][..] row stride kvs1 holding the first valid1 of the segment's Tk1 key slots (valid1 == rows1 == Tk1: no
+ * mask); optional second key / value segment k2 / v2 [B][Tk2][..] row stride kvs2 (`torch.cat([k, query_k], dim=2)`); head h at column h D of every row;
+ * out [B][Tq][H D] contiguous. */
+int selftok_ex_attention_f32(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
+                             long kvs2, int Tk2, float* out, void* workspace, int B, int H, int Tq, int D, hipStream_t stream)
+{
+    return ex_attention_unfused(q, qs, k1, v1, kvs1, Tk1, valid1, rows1, k2, v2, kvs2, Tk2, out, workspace, B, H, Tq, D, nullptr, 0, stream);
+}
+
+/* selftok_ex_attention_f32 with a visibility pattern over the first segment's slots (include/selftok_hip_ext.h) */
+int selftok_ex_attention_kmask_f32(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
+                                   long kvs2, int Tk2, float* out, void* workspace, int B, int H, int Tq, int D, const unsigned* kmask, long kmask_bs, hipStream_t stream)
+{
+    if (!kmask) { set_last_error("ex_attention_kmask: kmask is null"); return SELFTOK_EINVAL; }
+    return ex_attention_unfused(q, qs, k1, v1, kvs1, Tk1, valid1, rows1, k2, v2, kvs2, Tk2, out, workspace, B, H, Tq, D, kmask, kmask_bs, stream);
+}
+
 /* The same attention in ONE kernel (xe_fattn_kernel above): no workspace, no score matrix in HBM; bit-identical to selftok_ex_attention_f32.  head_dim 64, key
  * slot counts multiples of 64, and a last kv block (Tk mod 512) of at most 384 keys (one MKL K-block) -- else SELFTOK_EINVAL: use the unfused entry. */
 int selftok_ex_attention_fused_supported(int Tk1, int Tk2, int D)
@@ -1163,9 +1267,29 @@ int selftok_ex_attention_fused_supported(int Tk1, int Tk2, int D)
 int selftok_ex_attention_fused_f32(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
                                    long kvs2, int Tk2, float* out, int B, int H, int Tq, int D, hipStream_t stream)
 {
+    return ex_attention_fused(q, qs, k1, v1, kvs1, Tk1, valid1, rows1, k2, v2, kvs2, Tk2, out, B, H, Tq, D, nullptr, 0, stream);
+}
+
+/* selftok_ex_attention_fused_f32 with a visibility pattern over the first segment's slots (include/selftok_hip_ext.h) */
+int selftok_ex_attention_kmask_fused_f32(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
+                                         long kvs2, int Tk2, float* out, int B, int H, int Tq, int D, const unsigned* kmask, long kmask_bs, hipStream_t stream)
+{
+    if (!kmask) { set_last_error("ex_attention_kmask_fused: kmask is null"); return SELFTOK_EINVAL; }
+    return ex_attention_fused(q, qs, k1, v1, kvs1, Tk1, valid1, rows1, k2, v2, kvs2, Tk2, out, B, H, Tq, D, kmask, kmask_bs, stream);
+}
+
+}  // extern "C"
+
+static int ex_attention_fused(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
+                              long kvs2, int Tk2, float* out, int B, int H, int Tq, int D, const unsigned* kmask, long kmask_bs, hipStream_t stream)
+{
     if (B == 0) return SELFTOK_OK;
+    if (kmask && (Tk1 > 2048 || (kmask_bs != 0 && kmask_bs < (Tk1 + 31) / 32))) {
+        set_last_error("ex_attention_kmask_fused: need Tk1 <= 2048 and kmask_bs == 0 (one pattern) or >= ceil(Tk1 / 32)");
+        return SELFTOK_EINVAL;
+    }
     if (!q || !out || B < 0 || H <= 0 || Tq <= 0 || Tk1 < 0 || Tk2 < 0 || valid1 < 0 || valid1 > Tk1 || rows1 < valid1 || (valid1 > 0 && (!k1 || !v1)) || (Tk2 > 0 && (!k2 || !v2)) ||
-        qs % 4 || kvs1 % 4 || kvs2 % 4 || (valid1 == 0 && Tk2 == 0) || !selftok_ex_attention_fused_supported(Tk1, Tk2, D) ||
+        qs % 4 || kvs1 % 4 || kvs2 % 4 || (!kmask && valid1 == 0 && Tk2 == 0) || !selftok_ex_attention_fused_supported(Tk1, Tk2, D) ||
         (size_t)(rows1 > Tk2 ? rows1 : Tk2) * (size_t)(kvs1 > kvs2 ? kvs1 : kvs2) * 4 > 0xffffffffull) {
         set_last_error("ex_attention_fused: need head_dim 64, key slot counts % 64 == 0, a last kv block of <= 384 keys, 16-byte aligned rows, at least one visible key");
         return SELFTOK_EINVAL;
@@ -1174,8 +1298,8 @@ int selftok_ex_attention_fused_f32(const float* q, long qs, const float* k1, con
     a.q = q; a.qs = qs; a.k1 = k1; a.v1 = v1; a.kvs1 = kvs1; a.Tk1 = Tk1; a.valid1 = valid1; a.rows1 = rows1;
     a.k2 = k2; a.v2 = v2; a.kvs2 = kvs2; a.Tk2 = Tk2; a.out = out; a.B = B; a.H = H; a.Tq = Tq; a.qtiles = (Tq + 127) / 128;
     a.scale = (float)(1.0 / sqrt((double)D));
-    hipLaunchKernelGGL(xe_fattn_kernel, dim3((unsigned)(B * H * a.qtiles)), dim3(256), 0, stream, a);
+    a.kmask = kmask; a.kmask_bs = kmask_bs;
+    if (kmask) hipLaunchKernelGGL(xe_fattn_kernel<true>, dim3((unsigned)(B * H * a.qtiles)), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(xe_fattn_kernel<false>, dim3((unsigned)(B * H * a.qtiles)), dim3(256), 0, stream, a);
     return check_launch("xe_fattn_kernel");
 }
-
-}  // extern "C"

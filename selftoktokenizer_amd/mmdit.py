@@ -277,6 +277,13 @@ class MMDiTGPU(ModuleSurface):
         tab = [t[:n] for t in (tables or self.ctx_tables)]
         x = xe
         blk = "model.joint_blocks.{}.{}_block.{}".format
+        xmask = None                                            # gemm='exact': the words of the exact attention, the same for all 24 blocks
+        if self.gemm == "exact" and has_ctx:
+            xmask = kmask
+            if kvis is not None:
+                xmask = ops.pack_key_mask(torch.arange(self.K, device=x.device)[None] <= kvis.to(x.device)[:, None])
+            if xmask is not None and xmask.shape[1] * 32 < self.K:          # the kernel walks 64-slot tiles: words for every slot
+                xmask = torch.nn.functional.pad(xmask, (0, (self.K + 31) // 32 - xmask.shape[1])).contiguous()
 
         def attn_out(rows, consumer, zero=False):   # attention output buffer: split planes if the proj Linear takes them
             if self._pre(consumer) and amode:
@@ -293,16 +300,16 @@ class MMDiTGPU(ModuleSurface):
             if self.gemm == "exact":
                 # the joint attention as ATen's fp32 flash kernel evaluates `attention(q, k, v, heads, mask)` (sd3/other_impls.py:37-45) on the
                 # FULL key sequence [K context slots | image tokens] with the prefix mask: the n live context keys keep their positions (kv blocks
-                # of 512, MKL's K-blocks of 256 inside), the masked ones contribute exact zeros -- the same bits, not the truncated sequence's
-                if kvis is not None or kmask is not None:
-                    raise NotImplementedError("gemm='exact': one visibility prefix per call (the sampler's case); a per-sample `kvis` / `kmask` needs gemm='fp32' / 'f16x2'")
+                # of 512, MKL's K-blocks of 256 inside), the masked ones contribute exact zeros -- the same bits, not the truncated sequence's.
+                # Any other pattern (`kmask`; a per-sample `kvis` becomes prefix bits) takes the same walk with bit words: the n context rows stay at their
+                # positions 0 .. n - 1, an invisible one is a key nobody reads and a row nobody attends to (ATen's code path is the same for every bool mask)
                 xk, xv = xqkv[..., H:2 * H], xqkv[..., 2 * H:]
                 if has_ctx:
                     cqkv = cqkv0[:, :n].contiguous() if (i == 0 and cqkv0 is not None) else self.lin(pc + ".attn.qkv", cn)
                     ck, cv = cqkv[..., H:2 * H], cqkv[..., 2 * H:]
                     if not last:
-                        oc = ops.ex_attention(cqkv[..., :H], ck, cv, NH, xk if seg0_sees_seg1 else None, xv if seg0_sees_seg1 else None, slots1=self.K)
-                    ox = ops.ex_attention(xqkv[..., :H], ck, cv, NH, xk, xv, slots1=self.K)
+                        oc = ops.ex_attention(cqkv[..., :H], ck, cv, NH, xk if seg0_sees_seg1 else None, xv if seg0_sees_seg1 else None, slots1=self.K, kmask=xmask)
+                    ox = ops.ex_attention(xqkv[..., :H], ck, cv, NH, xk, xv, slots1=self.K, kmask=xmask)
                 else:
                     ox = ops.ex_attention(xqkv[..., :H], None, None, NH, xk, xv, slots1=self.K)        # cfg_inference: every context key masked
             ox = ox if self.gemm == "exact" else attn_out(nx, px + ".attn.proj")
@@ -373,7 +380,7 @@ class MMDiTGPU(ModuleSurface):
     def velocity_tokens(self, x, t_freq, ctx0, n_live: int, context_see_xt: bool = True, cqkv0=None, tables=None, t_key=None, kmask=None):
         """one model evaluation inside the sampler: returns the FinalLayer tokens [B,256,64].  `t_key`: a hashable name of the
         timestep t_freq embeds (the same for every sample), see `_step_modulations`.  `kmask`: per-sample visibility words over the
-        context rows (`core`); the kernel ignores the bits at and past n_live."""
+        context rows (`core`); the kernel ignores the bits at and past n_live.  gemm='exact' also takes one shared row [1, W]."""
         mods = self._step_modulations(t_freq, t_key)
         ctx = ctx0[:, :n_live].contiguous() if n_live < ctx0.shape[1] else ctx0
         return self.core(self.embed_image(x), None, ctx if n_live > 0 else None, context_see_xt, cqkv0=cqkv0 if n_live > 0 else None,
@@ -425,19 +432,21 @@ class MMDiTGPU(ModuleSurface):
             # the reference's own masks are prefixes (arange(K) <= k): the kvis path.  Any other [B, K] pattern (mask * super_mask) goes to the
             # attention kernel as per-sample bit words
             cnt = m.sum(dim=1)
-            if not bool((m == (torch.arange(m.shape[1], device=m.device)[None] < cnt[:, None])).all()):
-                if exact:
-                    raise NotImplementedError("MMDiTGPU.__call__: gemm='exact' takes prefix masks only (arange(K) <= k, models_ours.py:353); evaluate other "
-                                              "visibility patterns with gemm='fp32' / 'f16x2'")
-                kmask = self.pack_key_mask(m)
-            elif exact:
-                # gemm='exact' keeps every context key at its position in the reference's key sequence and takes ONE visibility prefix per call (the
-                # sampler's case): a batch-uniform mask is that prefix; a per-sample one would need the per-sample key walk the exact attention does not have
-                if not bool((cnt == cnt[0]).all()):
-                    raise NotImplementedError("gemm='exact': the mask must be the same prefix for every sample of the call (decode mixed prefixes in groups, or "
-                                              "with gemm='fp32' / 'f16x2')")
+            prefix = bool((m == (torch.arange(m.shape[1], device=m.device)[None] < cnt[:, None])).all())
+            if exact and prefix and bool((cnt == cnt[0]).all()):
+                # gemm='exact' keeps every context key at its position in the reference's key sequence; a batch-uniform prefix (the sampler's case) is the
+                # attention's own `valid1`
                 n_live = int(cnt[0])
                 ctx = ctx[:, :n_live].contiguous() if n_live > 0 else None
+            elif exact:
+                # any other [B, K] pattern, per-sample prefixes included: the context rows 0 .. n - 1 (n = the last position any sample sees, + 1) stay in
+                # place and the exact attention takes the bit words (selftok_ex_attention_kmask_*_f32)
+                pos = torch.nonzero(m.any(dim=0))
+                n_live = int(pos[-1]) + 1 if pos.numel() else 0
+                ctx = ctx[:, :n_live].contiguous() if n_live > 0 else None
+                kmask = self.pack_key_mask(m) if n_live > 0 else None
+            elif not prefix:
+                kmask = self.pack_key_mask(m)
             else:
                 kvis = (cnt - 1).to(torch.int32).contiguous()
         out = self.core(self.embed_image(x.to(self.device).float()), self.time_embed(t_freq), ctx, see, kvis, kmask=kmask)

@@ -769,7 +769,7 @@ def _rows2d(t: torch.Tensor):
     ld = t.stride(-2) if t.dim() > 1 else t.shape[-1]
     rows = t.numel() // t.shape[-1]
     for d in range(t.dim() - 2, 0, -1):                              # leading dims must step by whole row blocks
-        assert t.stride(d - 1) == t.stride(d) * t.shape[d], "rows are not equally strided"
+        assert t.shape[d - 1] == 1 or t.stride(d - 1) == t.stride(d) * t.shape[d], "rows are not equally strided"   # (the stride of a size-1 dim is never used)
     return rows, ld
 
 
@@ -915,13 +915,19 @@ EX_ATTENTION_WS_LIMIT = 6 << 30          # bytes of score workspace one call of 
 EX_ATTENTION_DEFAULT = "auto"     # what kernel='auto' means in ex_attention (tools set 'unfused' for A/B runs)
 
 
-def ex_attention(q: torch.Tensor, k1, v1, heads: int, k2=None, v2=None, slots1: Optional[int] = None, kernel: str = "auto") -> torch.Tensor:
+def ex_attention(q: torch.Tensor, k1, v1, heads: int, k2=None, v2=None, slots1: Optional[int] = None, kernel: str = "auto",
+                 kmask: Optional[torch.Tensor] = None, valid1: Optional[int] = None) -> torch.Tensor:
     """F.scaled_dot_product_attention as ATen's fp32 CPU flash kernel evaluates it.  q [B,Tq,H*D], k1 / v1 [B,Tk1,H*D] and an
     optional second key / value segment that follows the first; all may be column slices of fused projections.  -> [B,Tq,H*D].
     `slots1`: the first segment occupies slots1 >= Tk1 key positions of which only the Tk1 given ones are visible (a prefix mask: the
     masked keys keep their place in the kv blocks, see include/selftok_hip.h); k1 = v1 = None with slots1: none of them is visible.
     `kernel`: 'fused' = one kernel, scores never leave the CU (round 6: head_dim 64, slot counts % 64 == 0), 'unfused' = scores GEMM -> row pass -> P V GEMM through a
-    workspace (round 5, any shape), 'auto' = fused where it applies.  Same bits (tests/test_encoder_exact_gpu.py)."""
+    workspace (round 5, any shape), 'auto' = fused where it applies.  Same bits (tests/test_encoder_exact_gpu.py).
+    `kmask`: int32 [B, W] (or [1, W]: one pattern for the batch) words of `pack_key_mask` over the first segment's slots, W >= ceil(slots / 32): of the Tk1 given
+    rows (which stay at their positions 0 .. Tk1 - 1) only those whose bit is set are visible -- any pattern, the reference's `mask * super_mask`; the bits at
+    and past Tk1 are ignored.  An invisible row is never read into the arithmetic.  A sample without any visible key gets zeros.
+    `valid1` (with kmask): only the first valid1 <= Tk1 given rows can be visible, the bits at and past it are ignored too (the step prefix of `mask * super_mask`
+    over a buffer that holds more rows)."""
     if kernel == "auto":
         kernel = EX_ATTENTION_DEFAULT
     if kernel not in ("auto", "fused", "unfused"):
@@ -943,10 +949,25 @@ def ex_attention(q: torch.Tensor, k1, v1, heads: int, k2=None, v2=None, slots1: 
         Tk2, ks2 = k2.shape[1], _rows2d(k2)[1]
         assert _rows2d(v2)[1] == ks2 and k2.shape == v2.shape
     lib = _lib.load()
-    out = torch.empty(B, Tq, HD, dtype=torch.float32, device=q.device)
+    km_bs = 0
+    nv1 = rows1
+    if valid1 is not None:
+        assert kmask is not None and 0 <= int(valid1) <= rows1
+        nv1 = int(valid1)
+    if kmask is not None:
+        assert kmask.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and kmask.is_cuda and kmask.dim() == 2 and kmask.stride(1) == 1
+        assert kmask.shape[0] in (1, B) and kmask.shape[1] * 32 >= Tk1 and Tk1 <= 2048, (tuple(kmask.shape), B, Tk1)
+        km_bs = int(kmask.stride(0)) if kmask.shape[0] == B and B > 1 else 0
+    # with words a sample may have no visible key at all (no image keys, every context bit clear): its rows stay zero
+    out = (torch.zeros if (kmask is not None and Tk2 == 0) else torch.empty)(B, Tq, HD, dtype=torch.float32, device=q.device)
     if B == 0:
         return out
-    if kernel == "fused" or (kernel == "auto" and lib.selftok_ex_attention_fused_supported(Tk1, Tk2, D)):
+    fused = kernel == "fused" or (kernel == "auto" and lib.selftok_ex_attention_fused_supported(Tk1, Tk2, D))
+    if fused and kmask is not None:
+        _lib.check(lib.selftok_ex_attention_kmask_fused_f32(_p(q), qs, _p(k1), _p(v1), ks1, Tk1, nv1, rows1, _p(k2), _p(v2), ks2, Tk2, _p(out), B, heads, Tq, D,
+                                                            _p(kmask), km_bs, _stream()), "selftok_ex_attention_kmask_fused_f32")
+        return out
+    if fused:
         _lib.check(lib.selftok_ex_attention_fused_f32(_p(q), qs, _p(k1), _p(v1), ks1, Tk1, rows1, rows1, _p(k2), _p(v2), ks2, Tk2, _p(out), B, heads, Tq, D, _stream()),
                    "selftok_ex_attention_fused_f32")
         return out
@@ -958,6 +979,10 @@ def ex_attention(q: torch.Tensor, k1, v1, heads: int, k2=None, v2=None, slots1: 
     for b0 in range(0, B, nb):
         n = min(nb, B - b0)
         sl = lambda t: None if t is None else t[b0:b0 + n]
+        if kmask is not None:
+            _lib.check(lib.selftok_ex_attention_kmask_f32(_p(sl(q)), qs, _p(sl(k1)), _p(sl(v1)), ks1, Tk1, nv1, rows1, _p(sl(k2)), _p(sl(v2)), ks2, Tk2, _p(out[b0:b0 + n]), _p(ws),
+                                                          n, heads, Tq, D, _p(kmask[b0:b0 + n] if km_bs else kmask), km_bs, _stream()), "selftok_ex_attention_kmask_f32")
+            continue
         _lib.check(lib.selftok_ex_attention_f32(_p(sl(q)), qs, _p(sl(k1)), _p(sl(v1)), ks1, Tk1, rows1, rows1, _p(sl(k2)), _p(sl(v2)), ks2, Tk2, _p(out[b0:b0 + n]), _p(ws),
                                                 n, heads, Tq, D, _stream()), "selftok_ex_attention_f32")
     return out

@@ -105,7 +105,8 @@ class _Flow(FlowSchedule):
         """`prefix_k`: the reference loop's `super_mask` (rectified_flow.py:226-227, mask = mask * super_mask) for the prefix mask
         arange(K) < prefix_k -- only the first prefix_k tokens are ever visible (decode from a partial token sequence).
         `super_mask`: the same hook for ANY visibility pattern over the K tokens ([K] bool / 0-1, the same for every sample): the visible
-        tokens are gathered once (MMDiTGPU.gather_context) and the step mask is a prefix of that list.  `visible`: the same pattern
+        tokens are gathered once (MMDiTGPU.gather_context) and the step mask is a prefix of that list.  gemm='exact' gathers nothing: the
+        context rows keep their positions and the exact attention takes the pattern as bit words (selftok_ex_attention_kmask_*_f32).  `visible`: the same pattern
         already resolved by `resolve_super_mask` -- what a caller that captures this loop in a hipGraph passes (the resolution reads
         the mask on the host and uploads an index tensor, neither of which may happen while a stream is capturing).
         `key_mask`: a visibility pattern PER SAMPLE, decoded as one batch: `(words, rows)` = (device int32 [B, W] from
@@ -118,7 +119,8 @@ class _Flow(FlowSchedule):
             if visible is not None or super_mask is not None or prefix_k is not None:
                 raise ValueError("key_mask is exclusive with prefix_k / super_mask")
             if dit.gemm == "exact":
-                raise NotImplementedError("gemm='exact' reproduces the reference's bits for ONE prefix visibility pattern per call; decode per-sample patterns with gemm='fp32' / 'f16x2'")
+                raise NotImplementedError("gemm='exact' decodes ONE visibility pattern per sampler call; decode per-sample patterns in groups of equal pattern "
+                                          "(super_mask=tokens.suffix_mask(K, m) without mask_batched), or as one batch with gemm='fp32' / 'f16x2'")
             kwords, rows = key_mask
             rows = np.asarray(rows, dtype=bool)
             if rows.shape != (B, int(ehs.shape[1])) or tuple(kwords.shape) != (B, (rows.shape[1] + 31) // 32):
@@ -130,11 +132,15 @@ class _Flow(FlowSchedule):
         tables, vis_pos = None, None
         if visible is None and super_mask is not None:
             visible = self.resolve_super_mask(super_mask, ctx0.shape[1])
-        if visible is not None:
-            if dit.gemm == "exact" and not np.array_equal(visible[1], np.arange(len(visible[1]))):
-                # the exact mode keeps every context key at its POSITION in the reference's key sequence (kv blocks of 512, MKL's K-blocks); gathering the
-                # visible tokens of a non-prefix pattern moves them.  Prefix patterns (the sampler's own masks, prefix_k) are exact.
-                raise NotImplementedError("gemm='exact' reproduces the reference's bits for prefix visibility patterns; decode a non-prefix super_mask with gemm='fp32' / 'f16x2'")
+        exact_pos = None
+        if visible is not None and dit.gemm == "exact" and not np.array_equal(visible[1], np.arange(len(visible[1]))):
+            # the exact mode keeps every context key at its POSITION in the reference's key sequence (kv blocks of 512, MKL's K-blocks); gathering the
+            # visible tokens of a non-prefix pattern would move them.  So nothing is gathered: the rows 0 .. n_live - 1 stay in place and the exact
+            # attention takes the pattern as one shared row of bit words (device ops on the index made outside any capture: capturable)
+            idx_dev, exact_pos = visible
+            Kc = ctx0.shape[1]
+            kwords = dit.pack_key_mask(torch.zeros(Kc, dtype=torch.int64, device=self.device).scatter_(0, idx_dev, 1)[None])
+        elif visible is not None:
             idx_dev, vis_pos = visible                                        # device index tensor (made outside any capture), host positions
             ctx0, tables, _ = dit.gather_context(ctx0, index=idx_dev)
         cqkv0 = dit.block0_context_qkv(ctx0, tables) if ctx0.shape[1] > 0 else None   # block 0's context QKV is step independent too
@@ -147,6 +153,9 @@ class _Flow(FlowSchedule):
                 n_live = int(np.searchsorted(vis_pos, n_live, side="left"))
             if any_below is not None and not any_below[n_live]:               # no sample sees a key at this step: the n_live = 0 route
                 n_live = 0
+            if exact_pos is not None:                                         # rows up to the last visible position below n_live; none: the n_live = 0 route
+                below = int(np.searchsorted(exact_pos, n_live, side="left"))
+                n_live = int(exact_pos[below - 1]) + 1 if below > 0 else 0
             exact = dit.gemm == "exact" and self.t_freq_exact is not None
             tf = (self.t_freq_exact if exact else self.t_freq)[i:i + 1].expand(B, -1).contiguous()
             t_name = float(self.scheduled_t[i])                               # names the embedded timestep (MMDiTGPU._step_modulations)
@@ -391,7 +400,8 @@ class SelftokPipeline():
             differ = sm.dim() == 2 and sm.shape[0] == xt.shape[0] and not bool((sm == sm[:1]).all())
             if differ and mask_batched:
                 if self.model.model.gemm == "exact":
-                    raise NotImplementedError("gemm='exact' takes one prefix visibility pattern per call; decode per-sample patterns with gemm='fp32' / 'f16x2'")
+                    raise NotImplementedError("gemm='exact' decodes one visibility pattern per sampler call: pass super_mask=tokens.suffix_mask(K, m) without "
+                                              "mask_batched (groups of equal pattern), or decode the batch in one pass with gemm='fp32' / 'f16x2'")
                 if prefix_k is not None:
                     raise ValueError("mask_batched is exclusive with prefix_k")
                 rows = sm.reshape(sm.shape[0], -1).bool().numpy()

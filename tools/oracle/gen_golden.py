@@ -1,7 +1,7 @@
 """Generate tests/golden/*.npz by running the REFERENCE (read-only import, build container only) on the
 hash-generated synthetic weights/inputs, and report how oracle/ compares on the same inputs.
 
-    python tools/oracle/gen_golden.py [stage ...]      stages: keys vq schedule encoder dit vae pipeline pipeline16 encode64 renderer cfg k1024 vqtrain rmsnorm_rotary sampler_options
+    python tools/oracle/gen_golden.py [stage ...]      stages: keys vq schedule encoder dit vae pipeline pipeline16 encode64 renderer cfg k1024 vqtrain rmsnorm_rotary sampler_options exact_masks
 
 A golden file holds only data: inputs that cannot be regenerated from a seed, and the reference's
 outputs.  Weights/images/noise are regenerated from selftoktokenizer_amd.synth by name/seed.
@@ -1163,7 +1163,110 @@ def stage_rmsnorm_rotary():
     report("rmsnorm_rotary", arrays=sorted(out), rms_absmax=float(np.abs(out["rms_affine"]).max()), rot_absmax=float(np.abs(out["rot_full"]).max()))
 
 
-STAGES = dict(encoder_prenorm=stage_encoder_prenorm, pipeline64=stage_pipeline64, k1024_pipe16=stage_k1024_pipe16, renderer16=stage_renderer16, res128=lambda: stage_res(128), res320=lambda: stage_res(320), k1024_16=stage_k1024_16, cfg16=stage_cfg16, dit4=stage_dit4, config=stage_config, decode16=stage_decode16, encode64=stage_encode64, vq_entropy=stage_vq_entropy, rmsnorm_rotary=stage_rmsnorm_rotary, sampler_options=stage_sampler_options, ar_partial=stage_ar_partial, keys=stage_keys, vq=stage_vq, schedule=stage_schedule, encoder=stage_encoder, dit=stage_dit,
+def stage_exact_masks():
+    """non-prefix visibility masks in the exact-order regime (B = 16), for gemm='exact' with key bit masks.  First the HOST CHECK: the two guided steps of
+    stage_cfg16 are run again and their crc32 compared with the committed tests/golden/cfg_b16.npz -- do this host's torch / MKL / oneDNN paths give the bits the
+    committed goldens were made with?  Then (a) two sample_one_step steps with the hash pattern, (b) the same with the suffix m = 301, (c) one MMDiT.forward at
+    schedule index 30 with the per-sample mask of tests/ex_kmask_cases.model_rows, (d) K = 1024: one forward with the suffix m = 300 (the whole first kv block of
+    512 keys masked), (e) F.scaled_dot_product_attention with the bool mask on the hash-generated q / k / v of ex_kmask_cases.SDPA_CASES, output bits in full.
+    The report goes to tests/golden/PINNING_exact_masks.json."""
+    import zlib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ex_kmask_cases as XK
+    rep = {}
+    crc = lambda t: int(zlib.crc32(t.contiguous().numpy().tobytes()))
+    # (e) first: needs no model
+    sd_out = {}
+    for c in XK.SDPA_CASES:
+        q, ctx, img = XK.inputs(c)
+        o = XK.sdpa_aten(c, q, ctx, img, XK.case_mask(c))
+        assert bool(torch.isfinite(o).all())
+        sd_out[c.name] = o.numpy()
+        rep[f"sdpa/{c.name}"] = dict(crc=crc(o), absmax=float(o.abs().max()))
+    np.savez_compressed(os.path.join(GOLD, "ex_kmask_sdpa.npz"), **sd_out)
+
+    cfg, model, sd = tokenizer(CFG_256)
+    flow = _ref_flow()
+    from mimogpt.models.selftok.diti_utils import DiTi_cont
+    diti = DiTi_cont(1000, 512, cfg.tokenizer.params.stages, cfg.tokenizer.params.k_per_stage)
+    B, K = 16, 512
+    ids = torch.from_numpy(synth.synthetic_token_ids(B, first_index=11))
+    with torch.no_grad():
+        codes = model.encoder.quantizer.get_output_from_indices(ids)
+        ehs = model.encoder.final_layer_norm3(codes.reshape(B, -1, 16))
+    x = synth.synthetic_noise(B, first_index=11)
+
+    def steps(pattern, cfg_scale):
+        xr, crcs, subs, ks, vis = x.clone(), [], [], [], []
+        for i in (0, 1):
+            t = torch.tensor([flow.scheduled_t[i]] * B)
+            k = diti.to_indices(torch.tensor([flow.timestep_map[i]] * B).long())
+            mask = model.encoder.get_encoder_mask(x, k)
+            if pattern is not None:
+                mask = mask * torch.from_numpy(pattern)[None]
+            kw = dict(encoder_hidden_states=ehs, mask=mask, context_see_xt=True)
+            with torch.no_grad():
+                xr, _ = flow.sample_one_step(model.model, xr, t, index=i, model_kwargs=kw, cfg_scale=cfg_scale)
+            crcs.append(crc(xr)); subs.append(xr[:, :, ::4, ::4].contiguous().numpy()); ks.append(int(k[0])); vis.append(int(mask.reshape(B, -1)[0].sum()))
+        return crcs, subs, ks, vis
+
+    # the host check
+    old = np.load(os.path.join(GOLD, "cfg_b16.npz"))
+    crcs, _, _, _ = steps(None, 2.0)
+    same = [crcs[0] == int(old["crc_1"]), crcs[1] == int(old["crc_2"])]
+    rep["host_check"] = dict(cfg16_crc=crcs, committed=[int(old["crc_1"]), int(old["crc_2"])], same_bits=bool(all(same)), torch=torch.__version__,
+                             cpu_flags=sorted(f for f in open("/proc/cpuinfo").read().split("flags")[1].split("\n")[0].split() if f.startswith(("avx512", "amx"))))
+    print("[pin] host_check:", rep["host_check"], flush=True)
+
+    out = {"host_check_same_bits": np.bool_(all(same))}
+    for tag, pat in (("hash", XK.hash_pattern(K)), ("suffix301", XK.suffix(K, 301))):
+        crcs, subs, ks, vis = steps(pat, 1.0)
+        for i in (0, 1):
+            out[f"{tag}_crc_{i + 1}"] = np.uint32(crcs[i]); out[f"{tag}_sub_{i + 1}"] = subs[i]
+        out[f"{tag}_k"] = np.asarray(ks, np.int64); out[f"{tag}_visible"] = np.asarray(vis, np.int64)
+        rep[f"steps/{tag}"] = dict(k=ks, visible=vis, crc=crcs)
+    # (c) one forward with a mask per sample
+    i = 30
+    t = torch.tensor([flow.scheduled_t[i]] * B)
+    k = diti.to_indices(torch.tensor([flow.timestep_map[i]] * B).long())
+    mask = model.encoder.get_encoder_mask(x, k) * torch.from_numpy(XK.model_rows(K))
+    with torch.no_grad():
+        v, _ = model.model(x, t, None, ehs, mask=mask, context_see_xt=True)
+    assert bool(torch.isfinite(v).all())
+    out.update(fwd_crc=np.uint32(crc(v)), fwd_sub=v[:, :, ::4, ::4].contiguous().numpy(), fwd_index=np.int64(i), fwd_k=np.int64(int(k[0])),
+               fwd_visible=mask.reshape(B, -1).sum(dim=1).numpy().astype(np.int64))
+    rep["forward_per_sample"] = dict(k=int(k[0]), visible=[int(n) for n in out["fwd_visible"]], crc=crc(v))
+    np.savez_compressed(os.path.join(GOLD, "exact_masks_b16.npz"), **out)
+    json.dump(rep, open(os.path.join(GOLD, "PINNING_exact_masks.json"), "w"), indent=1, sort_keys=True)
+
+    # (d) K = 1024, the inputs of stage_k1024_16
+    _tok.clear()
+    del model, sd
+    cfg = H.load_cfg(CFG_256)
+    cfg.tokenizer.params.k = 1024
+    cfg.tokenizer.params.k_per_stage = "384,368,144,96,32"
+    model, ref_sd = H.build_tokenizer(cfg)
+    x0 = synth.synthetic_latents(B, first_index=5).to(torch.bfloat16).float()
+    with torch.no_grad():
+        outs_q, ids = model.encoder(x0, d=None)
+    from selftoktokenizer_amd.schedule import FlowSchedule, DiTiCont
+    fs = FlowSchedule(50, 1.0)
+    ktab = DiTiCont(1000, 1024, cfg.tokenizer.params.stages, cfg.tokenizer.params.k_per_stage).to_indices(fs.t_long)
+    i = 25
+    x = synth.synthetic_noise(B, first_index=5)
+    t = torch.full((B,), float(fs.scheduled_t[i]))
+    k = int(ktab[i])
+    mask = ((torch.arange(1024)[None] <= k) * torch.from_numpy(XK.suffix(1024, 300))[None]).expand(B, -1)
+    with torch.no_grad():
+        v, _ = model.model(x, t, encoder_hidden_states=outs_q, mask=mask, context_see_xt=True)
+    assert bool(torch.isfinite(v).all())
+    np.savez_compressed(os.path.join(GOLD, "exact_masks_k1024_b16.npz"), vcrc=np.uint32(crc(v)), vsub=v[:, :, ::4, ::4].contiguous().numpy(), step=np.int64(i),
+                        k=np.int64(k), visible=np.int64(int(mask[0].sum())), ids=ids.numpy().astype(np.int16))
+    rep["k1024_suffix300"] = dict(k=k, step=i, visible=int(mask[0].sum()), crc=crc(v))
+    json.dump(rep, open(os.path.join(GOLD, "PINNING_exact_masks.json"), "w"), indent=1, sort_keys=True)
+
+
+STAGES = dict(exact_masks=stage_exact_masks, encoder_prenorm=stage_encoder_prenorm, pipeline64=stage_pipeline64, k1024_pipe16=stage_k1024_pipe16, renderer16=stage_renderer16, res128=lambda: stage_res(128), res320=lambda: stage_res(320), k1024_16=stage_k1024_16, cfg16=stage_cfg16, dit4=stage_dit4, config=stage_config, decode16=stage_decode16, encode64=stage_encode64, vq_entropy=stage_vq_entropy, rmsnorm_rotary=stage_rmsnorm_rotary, sampler_options=stage_sampler_options, ar_partial=stage_ar_partial, keys=stage_keys, vq=stage_vq, schedule=stage_schedule, encoder=stage_encoder, dit=stage_dit,
               vae=stage_vae, pipeline=stage_pipeline, pipeline16=stage_pipeline16, renderer=stage_renderer, cfg=stage_cfg, k1024=stage_k1024, vqtrain=stage_vqtrain)
 
 if __name__ == "__main__":
@@ -1174,6 +1277,8 @@ if __name__ == "__main__":
         t0 = time.time()
         STAGES[n]()
         print(f"[stage] {n} done in {time.time() - t0:.1f}s", flush=True)
+    if not REPORT:                      # a stage with a report file of its own (exact_masks)
+        sys.exit(0)
     path = os.path.join(GOLD, "PINNING.json")
     old = json.load(open(path)) if os.path.exists(path) else {}
     old.update(REPORT)
