@@ -38,6 +38,35 @@ int selftok_ex_attention_kmask_f32(const float* q, long qs, const float* k1, con
 int selftok_ex_attention_kmask_fused_f32(const float* q, long qs, const float* k1, const float* v1, long kvs1, int Tk1, int valid1, int rows1, const float* k2, const float* v2,
                                          long kvs2, int Tk2, float* out, int B, int H, int Tq, int D, const unsigned* kmask, long kmask_bs, hipStream_t stream);
 
+/* ---- device image input: PIL-exact Resize(S) -> CenterCrop(S) -> NormalizeToTensor -------------------
+ * B RGB uint8 HWC images of different sizes, packed into one device buffer, -> out [B, 3, S, S] in [-1, 1].  `table` holds three longs
+ * per image: byte offset into `packed`, width, height; it is passed twice, readable by the host (validation, launch sizes) and by the
+ * device (the kernels) -- the same values, the caller's copy.  The device re-checks every image of ITS copy against the limits the host
+ * copy sized the launch and the workspace for: an image whose device entry disagrees is not processed -- its output planes are left
+ * untouched and the call still returns 0 (nothing is read or written outside; keeping the copies equal is the caller's duty).
+ * Per image, bit for bit what the reference's user script computes:
+ *   shorter side -> S, the other (int)(S * long / short); Pillow's 8-bit bilinear resample with antialias (ImagingResample: horizontal
+ *   pass first, uint8 between the passes, fp64 weights, 22-bit fixed-point coefficients, (2^21 + sum) >> 22, clip); a side that already
+ *   has its length is not resampled; centre crop at int(round((side - S) / 2.0)), half to even; then lut[u8].
+ * Only the crop window is resampled.  `lut`: 256 device values of the output type, float32(u8) / 127.5 - 1.0 made by the caller with the
+ * host expression it must equal (fp32, or that rounded to bf16).  out_bf16 != 0: out and lut are bf16, else fp32.
+ * Limits: 1 <= S <= 4096, 1 <= side <= 65536, a resized side < 2^30, offset + 3 * w * h <= packed_bytes.  The workspace (coefficient tables
+ * and the uint8 rows between the passes) is sized by the query from the same host table; 0 with selftok_last_error set on a bad table.
+ * After the call the workspace holds, per image b and output index i of the crop window, the tap rows
+ *   ((int*)workspace)[hdr + (b * S + i) * ks + {0: first input index, 1: taps n, 2 .. 2 + n: coefficients}]
+ * with hdr / ks / the vertical tables' base from selftok_img_resize_tables_layout (ints: [0] base of the horizontal tables,
+ * [1] their row stride, [2] base of the vertical tables, [3] their row stride; all in ints from the workspace start). */
+size_t selftok_img_resize_crop_norm_u8_workspace_bytes(const long* table_host, int B, int S);
+int selftok_img_resize_tables_layout(const long* table_host, int B, int S, long* layout4);
+int selftok_img_resize_crop_norm_u8(const unsigned char* packed, size_t packed_bytes, const long* table_host, const long* table_dev, int B, int S, void* out,
+                                    int out_bf16, const void* lut, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* ---- device image output: [B, 3, H, W] in [0, 1] -> uint8 [B, H, W, 3] ---------------------------------
+ * torchvision.utils.save_image's arithmetic in the tensor's own type: x * 255 rounded to the type, + 0.5 rounded to the type, clamp to
+ * [0, 255], truncate.  in_bf16 != 0: bf16 input, else fp32.  +Inf -> 255, -Inf -> 0; NaN -> 0 (this project's choice: torch's
+ * float -> uint8 conversion of NaN is undefined).  B * H * W < 2^31. */
+int selftok_img_to_u8(const void* img, int in_bf16, unsigned char* out, int B, int H, int W, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,10 @@ EXT_SIGNATURES = {
     "selftok_attn_kmask_f32": (_i, [_vp, _vp, _l, _vp]),
     "selftok_ex_attention_kmask_f32": (_i, [_vp, _l, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _l, _i, _vp, _vp, _i, _i, _i, _i, _vp, _l, _vp]),
     "selftok_ex_attention_kmask_fused_f32": (_i, [_vp, _l, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _l, _i, _vp, _i, _i, _i, _i, _vp, _l, _vp]),
+    "selftok_img_resize_crop_norm_u8_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "selftok_img_resize_tables_layout": (_i, [_vp, _i, _i, _vp]),
+    "selftok_img_resize_crop_norm_u8": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "selftok_img_to_u8": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
 }
 
 

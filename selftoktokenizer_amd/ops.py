@@ -986,3 +986,84 @@ def ex_attention(q: torch.Tensor, k1, v1, heads: int, k2=None, v2=None, slots1: 
         _lib.check(lib.selftok_ex_attention_f32(_p(sl(q)), qs, _p(sl(k1)), _p(sl(v1)), ks1, Tk1, rows1, rows1, _p(sl(k2)), _p(sl(v2)), ks2, Tk2, _p(out[b0:b0 + n]), _p(ws),
                                                 n, heads, Tq, D, _stream()), "selftok_ex_attention_f32")
     return out
+
+
+# ---- device image I/O (csrc/image_io.hip, include/selftok_hip_ext.h) ----
+_IMG_LUT = {}
+
+
+def image_norm_lut(device, dtype=torch.bfloat16) -> torch.Tensor:
+    """[256] of `dtype` on `device`: pipeline.NormalizeToTensor evaluated on every uint8 value (its own expression, so the two cannot drift)"""
+    import numpy as np
+    device = torch.device(device)
+    key = (device, dtype)
+    if key not in _IMG_LUT:
+        from .pipeline import NormalizeToTensor
+        lut = NormalizeToTensor()(np.arange(256, dtype=np.uint8).reshape(1, 256, 1)).reshape(256)
+        _IMG_LUT[key] = lut.to(dtype).to(device)
+    return _IMG_LUT[key]
+
+
+def _img_table(table):
+    import numpy as np
+    t = np.ascontiguousarray(np.asarray(table), dtype=np.int64)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise _lib.SelftokHipError(f"image table: expected [B, 3] (byte offset, width, height), got {t.shape}")
+    return t
+
+
+def image_resize_crop_norm(packed: torch.Tensor, table, size: int, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None,
+                           table_dev: Optional[torch.Tensor] = None, return_tables: bool = False):
+    """B RGB uint8 HWC images of any sizes, packed in the 1-D uint8 device tensor `packed`; `table` [B, 3] on the host: byte offset, width,
+    height of each.  -> [B, 3, size, size] in [-1, 1], bf16 or fp32: NormalizeToTensor(CenterCrop(size)(Resize(size)(PIL image))) bit for bit.
+    `table_dev`: the same table already on the device (int64), else it is copied here.  `out`: write into this contiguous tensor.
+    return_tables: also the integer tap rows the kernels used, {'h' | 'v': (first [B, size], n [B, size], k [B, size, kmax])} (tests)."""
+    import numpy as np
+    _need_cuda(packed, out, table_dev)
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise _lib.SelftokHipError(f"image_resize_crop_norm: `packed` must be a contiguous 1-D uint8 tensor, got {packed.dtype} {tuple(packed.shape)}")
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.SelftokHipError(f"image_resize_crop_norm: output dtype {dtype}: expected bfloat16 or float32")
+    t = _img_table(table)
+    B, S = t.shape[0], int(size)
+    lib = _lib.load()
+    nbytes = lib.selftok_img_resize_crop_norm_u8_workspace_bytes(t.ctypes.data, B, S)
+    if nbytes == 0:
+        _lib.check(-1, "selftok_img_resize_crop_norm_u8_workspace_bytes")
+    if table_dev is None:
+        table_dev = torch.from_numpy(t).to(packed.device)
+    elif table_dev.dtype != torch.int64 or table_dev.numel() != 3 * B or not table_dev.is_contiguous():
+        raise _lib.SelftokHipError("image_resize_crop_norm: `table_dev` must be the contiguous int64 [B, 3] table")
+    if out is None:
+        out = torch.empty(B, 3, S, S, dtype=dtype, device=packed.device)
+    elif out.dtype != dtype or tuple(out.shape) != (B, 3, S, S) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"image_resize_crop_norm: `out` must be a contiguous {dtype} [{B}, 3, {S}, {S}] tensor")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
+    lut = image_norm_lut(packed.device, dtype)
+    _lib.check(lib.selftok_img_resize_crop_norm_u8(_p(packed), packed.numel(), t.ctypes.data, _p(table_dev), B, S, _p(out), int(dtype == torch.bfloat16),
+                                                   _p(lut), _p(ws), nbytes, _stream()), "selftok_img_resize_crop_norm_u8")
+    if not return_tables:
+        return out
+    lay = np.zeros(4, dtype=np.int64)
+    _lib.check(lib.selftok_img_resize_tables_layout(t.ctypes.data, B, S, lay.ctypes.data), "selftok_img_resize_tables_layout")
+    wi = ws[:(nbytes // 4) * 4].view(torch.int32).cpu().numpy()
+    tabs = {}
+    for name, base, ks in (("h", int(lay[0]), int(lay[1])), ("v", int(lay[2]), int(lay[3]))):
+        rows = wi[base:base + B * S * ks].reshape(B, S, ks)
+        tabs[name] = (rows[:, :, 0].copy(), rows[:, :, 1].copy(), rows[:, :, 2:].copy())
+    return out, tabs
+
+
+def image_to_u8(img: torch.Tensor) -> torch.Tensor:
+    """[B, 3, H, W] in [0, 1], bf16 or fp32 -> uint8 [B, H, W, 3] with torchvision.utils.save_image's arithmetic in the tensor's own dtype
+    (x * 255, + 0.5, each rounded to the dtype, clamp to [0, 255], truncate); NaN -> 0"""
+    _need_cuda(img)
+    if img.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.SelftokHipError(f"image_to_u8: dtype {img.dtype}: expected bfloat16 or float32")
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise _lib.SelftokHipError(f"image_to_u8: expected [B, 3, H, W], got {tuple(img.shape)}")
+    img = img.contiguous()
+    B, _, H, W = img.shape
+    out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=img.device)
+    _lib.check(_lib.load().selftok_img_to_u8(_p(img), int(img.dtype == torch.bfloat16), _p(out), B, H, W, _stream()), "selftok_img_to_u8")
+    return out

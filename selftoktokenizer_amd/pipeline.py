@@ -317,6 +317,39 @@ class SelftokPipeline():
 
     @_on_own_device
     @torch.no_grad()
+    def preprocess_u8(self, images, dtype=None) -> torch.Tensor:
+        """(extension) uint8 RGB HWC images -- a list of arrays of ANY sizes, or one uint8 tensor [B, H, W, 3] (host or device) -> the
+        [B, 3, datasize, datasize] batch `encoding` takes, on the device: Resize(datasize) -> CenterCrop(datasize) -> NormalizeToTensor of
+        the reference's user script (test.py:27-31) bit for bit (csrc/image_io.hip).  dtype: this pipeline's bf16 (default) or fp32."""
+        dtype = dtype or self.dtype
+        if torch.is_tensor(images):
+            if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+                raise TypeError(f"expected a uint8 [B, H, W, 3] tensor, got {images.dtype} {tuple(images.shape)}")
+            if images.is_cuda:
+                B, H, W, _ = images.shape
+                table = np.array([[b * H * W * 3, W, H] for b in range(B)], dtype=np.int64)
+                return ops.image_resize_crop_norm(images.to(self.device).contiguous().reshape(-1), table, int(self.datasize), dtype=dtype)
+            images = list(images.numpy())
+        loaders = self.__dict__.setdefault("_u8_loaders", {})
+        if dtype not in loaders:
+            from .preprocess import DeviceLoader
+            loaders[dtype] = DeviceLoader(int(self.datasize), self.device, dtype=dtype)
+        return loaders[dtype].load(images)
+
+    def encoding_u8(self, images, device=None):
+        """(extension) `encoding` from 8-bit pixels: equal to encoding(torch.stack([load_image-equivalent of each image])) -- same bf16 tensor
+        into the VAE, same token ids -- without the per-image PIL resize, fp32 tensors and pageable copy on the host."""
+        return self.encoding(self.preprocess_u8(images), device=device)
+
+    @_on_own_device
+    @torch.no_grad()
+    def to_uint8(self, recons: torch.Tensor) -> torch.Tensor:
+        """(extension) the [0, 1] output of `decoding` / `decoding_with_renderer` -> uint8 [B, H, W, 3] on the device: the bytes
+        `preprocess.save_image` writes for each image (torchvision.utils.save_image's arithmetic in the tensor's own dtype)."""
+        return ops.image_to_u8(recons.to(self.device))
+
+    @_on_own_device
+    @torch.no_grad()
     def _codes(self, idx) -> torch.Tensor:
         if isinstance(idx, np.ndarray):
             if not np.issubdtype(idx.dtype, np.integer):

@@ -110,3 +110,16 @@ def synthetic_token_ids(batch: int, K: int = 512, codebook_size: int = 32768, fi
 def synthetic_vq_rows(n: int, dim: int = 16, device="cpu", seed: int = 0xC0DE) -> torch.Tensor:
     """[n,dim] fp32 pre-normalisation encoder features for the VQ micro-benchmark."""
     return hash_normalish(seed, (n, dim), device)
+
+
+U8_IMAGE_SIZES = ((500, 375), (375, 500), (640, 427), (256, 256), (300, 300), (1024, 768), (257, 256), (333, 500))   # (width, height)
+
+
+def synthetic_u8_images(batch: int, first_index: int = 0, sizes=U8_IMAGE_SIZES):
+    """`batch` RGB uint8 HWC arrays of mixed sizes (image i: sizes[i % len(sizes)], hash bytes of seed IMAGE_SEED + i): the input of
+    the device image loader (preprocess.DeviceLoader, SelftokPipeline.encoding_u8), standing in for decoded files."""
+    out = []
+    for i in range(first_index, first_index + batch):
+        w, h = sizes[i % len(sizes)]
+        out.append((hash_u32(IMAGE_SEED + i, h * w * 3) >> 13 & 0xFF).to(torch.uint8).reshape(h, w, 3).numpy())
+    return out

@@ -27,6 +27,7 @@ ap.add_argument("--data_size", type=int, default=256)
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--seed", type=int, default=1234)
 ap.add_argument("--gemm", default=None, choices=["fp32", "f16x2", "exact"], help="exact: every operation in the reference's torch-CPU order (bit-equal pixels, the parity mode)")
+ap.add_argument("--device-io", action="store_true", help="resize / crop / normalise the decoded files on the GPU (preprocess.DeviceLoader): the same values, bit for bit")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file (rank 0)")
 a = ap.parse_args()
 
@@ -56,7 +57,7 @@ else:
     if a.limit:
         paths = paths[:a.limit]
     assert paths, f"no image files under {a.images}"
-    n, load, noise, src = len(paths), E.folder_loader(paths, a.data_size), None, f"{len(paths)} files under {a.images}"
+    n, load, noise, src = len(paths), E.folder_loader(paths, a.data_size, device=dev if a.device_io else None), None, f"{len(paths)} files under {a.images}"
 res = E.evaluate(pipe, load, n, batch=a.batch, decoders=decoders, noise_fn=noise, seed=a.seed, renderer_pipe=rpipe, verbose=True)
 D.barrier()
 if rank == 0:

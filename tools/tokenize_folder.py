@@ -1,0 +1,87 @@
+"""Tokenise an image folder on MI355X: files -> host decode (thread pool) -> pinned staging -> one H2D copy -> resize / crop / normalise on the
+GPU (csrc/image_io.hip, the reference's PIL arithmetic bit for bit) -> `encoding` -> token ids.  Sharded over ranks under torchrun.
+
+    python tools/tokenize_folder.py --images <dir> --yml-path configs/res256/256-eval.yml --pretrained tokenizer_512_ckpt.pth --sd3_pretrained <sd3 dir> --out ids
+    python tools/tokenize_folder.py --synthetic 256 --out /tmp/ids          # hash-generated weights and mixed-size uint8 images
+
+Every rank writes <out>.rank<r>.npy (int64 [n, K], what the reference script saves; --uint16 for the compact wire format) and rank 0 prints
+ONE JSON line: images/s and where the time went (host decode, pack, H2D copy, resize kernels, encode)."""
+import argparse, json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from mimogpt.infer.infer_utils import parse_args_from_yaml
+from mimogpt.infer.SelftokPipeline import SelftokPipeline
+from selftoktokenizer_amd import dist as D, evaluate as E, preprocess, synth, tokens, weights as W
+from selftoktokenizer_amd.config import default_config
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--images", default=None, help="folder of images (searched recursively, sorted)")
+ap.add_argument("--synthetic", type=int, default=0, help="N hash-generated mixed-size uint8 images + synthetic weights instead of files")
+ap.add_argument("--limit", type=int, default=0)
+ap.add_argument("--yml-path", default=None)
+ap.add_argument("--pretrained", default=None)
+ap.add_argument("--sd3_pretrained", default=None)
+ap.add_argument("--data_size", type=int, default=256)
+ap.add_argument("--batch", type=int, default=64)
+ap.add_argument("--workers", type=int, default=8, help="host decode threads (at most 16)")
+ap.add_argument("--encoder-mode", default=None, choices=["exact", "fast"])
+ap.add_argument("--vae-mode", default=None, choices=["exact", "parity", "fast", "miopen"])
+ap.add_argument("--uint16", action="store_true", help="write tokens.to_uint16 ids instead of the reference's int64")
+ap.add_argument("--out", default=None, help="prefix of the id files; nothing is written without it")
+a = ap.parse_args()
+
+rank, world, local = D.init_from_env()
+torch.cuda.set_device(local)
+dev = torch.device("cuda", local)
+cfg = parse_args_from_yaml(a.yml_path) if a.yml_path else default_config(512)
+K = int(cfg.tokenizer.params.k)
+kw = {}
+if a.pretrained is None:
+    kw = dict(state_dict=W.synthetic_state_dict(W.expected_shapes(K), device=dev), vae_state_dict=W.synthetic_vae_state_dict(device=dev))
+pipe = SelftokPipeline(cfg=cfg, ckpt_path=a.pretrained, sd3_path=a.sd3_pretrained, datasize=a.data_size, device=dev, verbose=False,
+                       encoder_mode=a.encoder_mode, vae_mode=a.vae_mode, **kw)
+if a.synthetic:
+    n, src = a.synthetic, f"{a.synthetic} hash-generated uint8 images (selftoktokenizer_amd.synth)"
+    lo, hi = D.shard_range(n, rank, world)
+    items = synth.synthetic_u8_images(hi - lo, first_index=lo)
+else:
+    assert a.images, "--images <dir> or --synthetic N"
+    paths = E.list_images(a.images)
+    paths = paths[:a.limit] if a.limit else paths
+    assert paths, f"no image files under {a.images}"
+    n, src = len(paths), f"{len(paths)} files under {a.images}"
+    lo, hi = D.shard_range(n, rank, world)
+    items = paths[lo:hi]
+
+loader = preprocess.DeviceLoader(a.data_size, dev, dtype=torch.bfloat16, workers=a.workers)
+loader.timing = True
+ids, split, marks = [], {"host_decode_s": 0.0, "pack_s": 0.0, "h2d_ms": 0.0, "resize_kernels_ms": 0.0, "encode_ms": 0.0}, []
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+for batch in loader.batches(items, a.batch):
+    ev, lt = loader.last_events, loader.last_times
+    e3 = torch.cuda.Event(enable_timing=True)
+    tok = pipe.encoding(batch, device=dev)
+    e3.record()
+    marks.append(ev + (e3,))
+    split["host_decode_s"] += lt["decode_s"]; split["pack_s"] += lt["pack_s"]
+    ids.append(tok.cpu().numpy())
+torch.cuda.synchronize()
+wall = time.perf_counter() - t0
+for e0, e1, e2, e3 in marks:
+    split["h2d_ms"] += e0.elapsed_time(e1); split["resize_kernels_ms"] += e1.elapsed_time(e2); split["encode_ms"] += e2.elapsed_time(e3)
+loader.close()
+ids = np.concatenate(ids) if ids else np.zeros((0, K), np.int64)
+if a.out:
+    f = f"{a.out}.rank{rank}.npy"
+    np.save(f, tokens.to_uint16(ids)) if a.uint16 else tokens.save_reference_npy(f, ids)
+slowest = D.max_over_ranks(wall, dev)
+D.barrier()
+if rank == 0:
+    print(json.dumps({"tool": "tokenize_folder", "source": src, "images": n, "ranks": world, "batch": a.batch, "workers": loader.workers, "tokens": K,
+                      "data_size": a.data_size, "vae": pipe.vae.mode, "encoder": pipe.model.encoder.mode, "wall_s": round(slowest, 4),
+                      "images_per_s": round(n / slowest, 2) if slowest > 0 else None,
+                      "rank0_split": {k: round(v, 4) for k, v in split.items()}, "rank0_shard": [lo, hi],
+                      "note": "host decode / pack of batch i + 1 overlap the GPU work of batch i, so the parts do not add up to wall_s"}), flush=True)
+D.shutdown()
