@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from . import ops
 from .modsurface import ModuleSurface
 from .encoder import sinusoid_host
-from .schedule import DiTiCont
+from .schedule import DiTiCont, last_visible, prefix_lengths, rows_uniform
 from .weights import DIT_DEPTH, DIT_HEADS, DIT_HIDDEN, POS_MAX_DIT
 
 
@@ -259,6 +259,51 @@ class MMDiTGPU(ModuleSurface):
             self._mod_cache[key] = mods
         return mods
 
+    def _joint_attention(self, xe: torch.Tensor, n: int, seg0_sees_seg1: bool, kvis, kmask):
+        """-> attend(block, xqkv, cqkv or None) -> (oc, ox): the joint attention of `core`'s blocks over n context rows and xe's image rows.  oc is
+        None without context rows and in the last block (pre_only: keys / values only, its attention output is discarded, sd3/mmdit.py:544-547)."""
+        H, NH = DIT_HIDDEN, DIT_HEADS
+        (B, nx, _), dev, last = xe.shape, xe.device, DIT_DEPTH - 1
+        if self.gemm == "exact":
+            # as ATen's fp32 flash kernel evaluates `attention(q, k, v, heads, mask)` (sd3/other_impls.py:37-45) on the FULL key sequence [K context
+            # slots | image tokens] with the prefix mask: the n live context keys keep their positions (kv blocks of 512, MKL's K-blocks of 256 inside),
+            # the masked ones contribute exact zeros -- the same bits, not the truncated sequence's.  Any other pattern (`kmask`; a per-sample `kvis`
+            # becomes prefix bits) takes the same walk with bit words, the same for all 24 blocks: the n context rows stay at their positions 0 .. n - 1,
+            # an invisible one is a key nobody reads and a row nobody attends to (ATen's code path is the same for every bool mask)
+            if n > 0 and kvis is not None:
+                kmask = ops.pack_key_mask(torch.arange(self.K, device=dev)[None] <= kvis.to(dev)[:, None])
+            if n > 0 and kmask is not None and kmask.shape[1] * 32 < self.K:          # the kernel walks 64-slot tiles: words for every slot
+                kmask = F.pad(kmask, (0, (self.K + 31) // 32 - kmask.shape[1])).contiguous()
+
+            def attend(i, xqkv, cqkv):
+                xq, xk, xv = xqkv[..., :H], xqkv[..., H:2 * H], xqkv[..., 2 * H:]
+                if cqkv is None:
+                    return None, ops.ex_attention(xq, None, None, NH, xk, xv, slots1=self.K)       # cfg_inference: every context key masked
+                cqkv = cqkv.contiguous()
+                cq, ck, cv = cqkv[..., :H], cqkv[..., H:2 * H], cqkv[..., 2 * H:]
+                see = (xk, xv) if seg0_sees_seg1 else (None, None)
+                oc = None if i == last else ops.ex_attention(cq, ck, cv, NH, *see, slots1=self.K, kmask=kmask)
+                return oc, ops.ex_attention(xq, ck, cv, NH, xk, xv, slots1=self.K, kmask=kmask)
+            return attend
+        amode = ops.ATTN_F16X2 if self.gemm == "f16x2" else 0   # 'f16x2': the joint attention runs as split products too
+
+        def out(rows, consumer, zero=False):        # attention output buffer: split planes if the proj Linear takes them
+            if self._pre(consumer) and amode:
+                return ops.SplitAct((B, rows, H), dev, zero=zero)
+            return (torch.zeros if zero else torch.empty)(B, rows, H, device=dev)
+
+        def attend(i, xqkv, cqkv):                  # a strided [:, :n] view of a precomputed cqkv is fine
+            ox = out(nx, f"model.joint_blocks.{i}.x_block.attn.proj")
+            seg1 = (xqkv[..., :H], xqkv[..., H:2 * H], xqkv[..., 2 * H:], ox)
+            if cqkv is None:
+                ops.attention(None, seg1, NH, 64, mode=amode, overflow=self.overflow)
+                return None, ox
+            oc = None if i == last else out(n, f"model.joint_blocks.{i}.context_block.attn.proj", zero=kvis is not None or kmask is not None)
+            seg0 = (None if i == last else cqkv[..., :H], cqkv[..., H:2 * H], cqkv[..., 2 * H:], oc)
+            ops.attention(seg0, seg1, NH, 64, kvis=kvis, seg0_sees_seg1=seg0_sees_seg1, mode=amode, overflow=self.overflow, kmask=kmask)
+            return oc, ox
+        return attend
+
     @torch.no_grad()
     def core(self, xe: torch.Tensor, c: Optional[torch.Tensor], ctx: Optional[torch.Tensor], seg0_sees_seg1: bool = True,
              kvis: Optional[torch.Tensor] = None, cqkv0: Optional[torch.Tensor] = None, tables=None, mods=None,
@@ -268,28 +313,14 @@ class MMDiTGPU(ModuleSurface):
         context rows (`pack_key_mask`; exclusive with kvis; bits past n_ctx are ignored), the same words for all 24 blocks.  `tables`: per-block context adaLN tables whose row j belongs to context
         row j (default: the position tables; `gather_context` returns the rows of a visibility pattern).  `mods`: the result of
         `modulations(c, ...)` if the caller already has it (c is then unused)."""
-        H, NH = DIT_HIDDEN, DIT_HEADS
-        B, nx, _ = xe.shape
+        H = DIT_HIDDEN
         n = 0 if ctx is None else ctx.shape[1]
         has_ctx = n > 0
-        amode = ops.ATTN_F16X2 if self.gemm == "f16x2" else 0   # 'f16x2': the joint attention runs as split products too
         mods_x, mods_c_last, mods_f = mods if mods is not None else self.modulations(c, has_ctx)
         tab = [t[:n] for t in (tables or self.ctx_tables)]
         x = xe
         blk = "model.joint_blocks.{}.{}_block.{}".format
-        xmask = None                                            # gemm='exact': the words of the exact attention, the same for all 24 blocks
-        if self.gemm == "exact" and has_ctx:
-            xmask = kmask
-            if kvis is not None:
-                xmask = ops.pack_key_mask(torch.arange(self.K, device=x.device)[None] <= kvis.to(x.device)[:, None])
-            if xmask is not None and xmask.shape[1] * 32 < self.K:          # the kernel walks 64-slot tiles: words for every slot
-                xmask = torch.nn.functional.pad(xmask, (0, (self.K + 31) // 32 - xmask.shape[1])).contiguous()
-
-        def attn_out(rows, consumer, zero=False):   # attention output buffer: split planes if the proj Linear takes them
-            if self._pre(consumer) and amode:
-                return ops.SplitAct((B, rows, H), x.device, zero=zero)
-            return (torch.zeros if zero else torch.empty)(B, rows, H, device=x.device)
-
+        attend = self._joint_attention(xe, n, seg0_sees_seg1, kvis, kmask)
         _, xn = self._ln(blk(0, "x", "attn.qkv"), x, shift=mods_x[0][:, 0:H], scale=mods_x[0][:, H:2 * H], per_sample=True)
         if has_ctx and cqkv0 is None:
             _, cn = self._ln(blk(0, "context", "attn.qkv"), ctx, shift=tab[0][:, 0:H], scale=tab[0][:, H:2 * H])
@@ -297,36 +328,10 @@ class MMDiTGPU(ModuleSurface):
             pc, px = f"model.joint_blocks.{i}.context_block", f"model.joint_blocks.{i}.x_block"
             last = i == DIT_DEPTH - 1
             xqkv = self.lin(px + ".attn.qkv", xn)                                  # [B,nx,3H]
-            if self.gemm == "exact":
-                # the joint attention as ATen's fp32 flash kernel evaluates `attention(q, k, v, heads, mask)` (sd3/other_impls.py:37-45) on the
-                # FULL key sequence [K context slots | image tokens] with the prefix mask: the n live context keys keep their positions (kv blocks
-                # of 512, MKL's K-blocks of 256 inside), the masked ones contribute exact zeros -- the same bits, not the truncated sequence's.
-                # Any other pattern (`kmask`; a per-sample `kvis` becomes prefix bits) takes the same walk with bit words: the n context rows stay at their
-                # positions 0 .. n - 1, an invisible one is a key nobody reads and a row nobody attends to (ATen's code path is the same for every bool mask)
-                xk, xv = xqkv[..., H:2 * H], xqkv[..., 2 * H:]
-                if has_ctx:
-                    cqkv = cqkv0[:, :n].contiguous() if (i == 0 and cqkv0 is not None) else self.lin(pc + ".attn.qkv", cn)
-                    ck, cv = cqkv[..., H:2 * H], cqkv[..., 2 * H:]
-                    if not last:
-                        oc = ops.ex_attention(cqkv[..., :H], ck, cv, NH, xk if seg0_sees_seg1 else None, xv if seg0_sees_seg1 else None, slots1=self.K, kmask=xmask)
-                    ox = ops.ex_attention(xqkv[..., :H], ck, cv, NH, xk, xv, slots1=self.K, kmask=xmask)
-                else:
-                    ox = ops.ex_attention(xqkv[..., :H], None, None, NH, xk, xv, slots1=self.K)        # cfg_inference: every context key masked
-            ox = ox if self.gemm == "exact" else attn_out(nx, px + ".attn.proj")
-            seg1 = (xqkv[..., :H], xqkv[..., H:2 * H], xqkv[..., 2 * H:], ox)
-            if self.gemm == "exact":
-                pass
-            elif has_ctx:
-                # [B,n,3H]; block 0's is step-invariant and may come precomputed (a strided [:, :n] view is fine)
+            cqkv = None                                                            # [B,n,3H]; block 0's is step-invariant and may come precomputed
+            if has_ctx:
                 cqkv = cqkv0[:, :n] if (i == 0 and cqkv0 is not None) else self.lin(pc + ".attn.qkv", cn)
-                if last:   # pre_only context block: keys/values only, its attention output is discarded (sd3/mmdit.py:544-547)
-                    seg0 = (None, cqkv[..., H:2 * H], cqkv[..., 2 * H:], None)
-                else:
-                    oc = attn_out(n, pc + ".attn.proj", zero=kvis is not None or kmask is not None)
-                    seg0 = (cqkv[..., :H], cqkv[..., H:2 * H], cqkv[..., 2 * H:], oc)
-                ops.attention(seg0, seg1, NH, 64, kvis=kvis, seg0_sees_seg1=seg0_sees_seg1, mode=amode, overflow=self.overflow, kmask=kmask)
-            else:
-                ops.attention(None, seg1, NH, 64, mode=amode, overflow=self.overflow)
+            oc, ox = attend(i, xqkv, cqkv)
             # ---- context stream post-attention (sd3/mmdit.py:485-496, 'pos_emb') ----
             if has_ctx and not last:
                 t = tab[i]
@@ -428,27 +433,21 @@ class MMDiTGPU(ModuleSurface):
         ctx = self.embed_context(ehs)
         kvis = kmask = None
         if mask is not None:
-            m = mask.to(self.device).bool()
-            # the reference's own masks are prefixes (arange(K) <= k): the kvis path.  Any other [B, K] pattern (mask * super_mask) goes to the
-            # attention kernel as per-sample bit words
-            cnt = m.sum(dim=1)
-            prefix = bool((m == (torch.arange(m.shape[1], device=m.device)[None] < cnt[:, None])).all())
-            if exact and prefix and bool((cnt == cnt[0]).all()):
-                # gemm='exact' keeps every context key at its position in the reference's key sequence; a batch-uniform prefix (the sampler's case) is the
-                # attention's own `valid1`
-                n_live = int(cnt[0])
+            # the reference's own masks are prefixes (arange(K) <= k): the kvis path.  Any other [B, K] pattern (mask * super_mask) goes to the attention
+            # kernel as per-sample bit words.  gemm='exact' keeps every context key at its position in the reference's key sequence: the rows 0 .. n - 1
+            # (n = the last position any sample sees, + 1) stay in place, under the words (selftok_ex_attention_kmask_*_f32) unless the mask is one prefix
+            # for the whole batch (the sampler's case): that is the attention's own `valid1`
+            rows = mask.cpu().numpy() != 0                                  # the one host copy: the predicates are schedule.py's, as in context_plan
+            cnt = prefix_lengths(rows)
+            if exact:
+                words = cnt is None or not rows_uniform(rows)
+                n_live = last_visible(rows)
                 ctx = ctx[:, :n_live].contiguous() if n_live > 0 else None
-            elif exact:
-                # any other [B, K] pattern, per-sample prefixes included: the context rows 0 .. n - 1 (n = the last position any sample sees, + 1) stay in
-                # place and the exact attention takes the bit words (selftok_ex_attention_kmask_*_f32)
-                pos = torch.nonzero(m.any(dim=0))
-                n_live = int(pos[-1]) + 1 if pos.numel() else 0
-                ctx = ctx[:, :n_live].contiguous() if n_live > 0 else None
-                kmask = self.pack_key_mask(m) if n_live > 0 else None
-            elif not prefix:
-                kmask = self.pack_key_mask(m)
+                kmask = self.pack_key_mask(torch.from_numpy(rows).to(self.device)) if (words and n_live > 0) else None
+            elif cnt is None:
+                kmask = self.pack_key_mask(torch.from_numpy(rows).to(self.device))
             else:
-                kvis = (cnt - 1).to(torch.int32).contiguous()
+                kvis = torch.from_numpy((cnt - 1).astype(np.int32)).to(self.device)
         out = self.core(self.embed_image(x.to(self.device).float()), self.time_embed(t_freq), ctx, see, kvis, kmask=kmask)
         _, v = ops.unpatchify_cfg_euler(out, C=16, hp=Hh // 2, wp=Ww // 2)
         return v, torch.zeros(B, dtype=torch.bool)

@@ -15,11 +15,11 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, gemm_tune, ops, tokens, weights as W
+from . import _lib, gemm_tune, ops, weights as W
 from .encoder import QformerEncoderGPU, sinusoid_host
 from .mmdit import MMDiTGPU
 from .modsurface import ModuleSurface
-from .schedule import DiTiCont, FlowSchedule
+from .schedule import DiTiCont, FlowSchedule, context_plan, pattern_groups, request_pattern
 from .vae import AutoencoderKLGPU
 
 SD3_SCALE, SD3_SHIFT = 1.5305, 0.0609     # SD3LatentFormat (sd3/sd3_impls.py:136-138)
@@ -86,88 +86,52 @@ class _Flow(FlowSchedule):
             tab = torch.from_numpy(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "flow50_t_sincos.npy")))
             self.t_freq_exact, self.t_freq_uncond_exact = tab[0].to(device).contiguous(), tab[1].to(device).contiguous()
 
-    def resolve_super_mask(self, super_mask, K: int):
-        """[K] (or batch-uniform [B,K]) visibility pattern -> (device int64 index of the visible tokens, their positions as numpy)"""
-        sm = torch.as_tensor(super_mask).cpu()
-        if sm.dim() == 2:
-            if not bool((sm == sm[:1]).all()):      # SelftokPipeline._sample splits such a batch into groups of equal pattern before it gets here
-                raise NotImplementedError("p_sample_loop takes ONE visibility pattern per call (decode the samples in groups of equal pattern)")
-            sm = sm[0]
-        if sm.numel() != K:
-            raise ValueError(f"super_mask has {sm.numel()} entries, the tokenizer has K = {K} tokens")
-        vis_pos = np.nonzero(sm.reshape(-1).bool().numpy())[0].astype(np.int64)
-        return torch.from_numpy(vis_pos).to(self.device), vis_pos
+    def plan_context(self, dit: MMDiTGPU, k_table, K: int, prefix_k: Optional[int] = None, super_mask=None, batched: bool = False):
+        """-> (schedule.ContextPlan, device index of its `gather`, device words of its `words_rows`; None where the plan has none): `p_sample_loop`'s
+        `plan=`.  It reads the mask on the host and uploads, neither of which may happen while a stream is capturing: a caller that captures the
+        loop in a hipGraph calls this first and keeps the result for as long as the graph lives."""
+        pattern = None if super_mask is None else torch.as_tensor(super_mask).cpu().numpy()
+        plan = context_plan(k_table, K, len(k_table), prefix_k, pattern, batched, keep_positions=dit.gemm == "exact")
+        index = None if plan.gather is None else torch.tensor(plan.gather, device=self.device)                    # (the plan's arrays are read-only: copy)
+        words = None if plan.words_rows is None else dit.pack_key_mask(torch.tensor(plan.words_rows, device=self.device))
+        return plan, index, words
 
     @torch.no_grad()
     def p_sample_loop(self, dit: MMDiTGPU, noise: torch.Tensor, ehs: torch.Tensor, k_table: np.ndarray,
                       context_see_xt: bool = True, uncond_scale: float = 1.0, max_steps: Optional[int] = None,
-                      trace: Optional[list] = None, prefix_k: Optional[int] = None, super_mask=None, visible=None, key_mask=None) -> torch.Tensor:
+                      trace: Optional[list] = None, prefix_k: Optional[int] = None, super_mask=None, plan=None) -> torch.Tensor:
         """`prefix_k`: the reference loop's `super_mask` (rectified_flow.py:226-227, mask = mask * super_mask) for the prefix mask
         arange(K) < prefix_k -- only the first prefix_k tokens are ever visible (decode from a partial token sequence).
-        `super_mask`: the same hook for ANY visibility pattern over the K tokens ([K] bool / 0-1, the same for every sample): the visible
-        tokens are gathered once (MMDiTGPU.gather_context) and the step mask is a prefix of that list.  gemm='exact' gathers nothing: the
-        context rows keep their positions and the exact attention takes the pattern as bit words (selftok_ex_attention_kmask_*_f32).  `visible`: the same pattern
-        already resolved by `resolve_super_mask` -- what a caller that captures this loop in a hipGraph passes (the resolution reads
-        the mask on the host and uploads an index tensor, neither of which may happen while a stream is capturing).
-        `key_mask`: a visibility pattern PER SAMPLE, decoded as one batch: `(words, rows)` = (device int32 [B, W] from
-        MMDiTGPU.pack_key_mask, the same masks as a host bool array [B, K]), both made before the loop (and before any capture).  The
-        joint attention takes the words (selftok_attn_kmask_f32) and ignores the bits at and past a step's n_live; the host copy only
-        decides whether a step has any visible key at all."""
-        B = noise.shape[0]
-        kwords = any_below = None
-        if key_mask is not None:
-            if visible is not None or super_mask is not None or prefix_k is not None:
-                raise ValueError("key_mask is exclusive with prefix_k / super_mask")
-            if dit.gemm == "exact":
-                raise NotImplementedError("gemm='exact' decodes ONE visibility pattern per sampler call; decode per-sample patterns in groups of equal pattern "
-                                          "(super_mask=tokens.suffix_mask(K, m) without mask_batched), or as one batch with gemm='fp32' / 'f16x2'")
-            kwords, rows = key_mask
-            rows = np.asarray(rows, dtype=bool)
-            if rows.shape != (B, int(ehs.shape[1])) or tuple(kwords.shape) != (B, (rows.shape[1] + 31) // 32):
-                raise ValueError(f"key_mask: expected words [B, ceil(K/32)] and rows [B, K] = [{B}, {int(ehs.shape[1])}]")
-            any_below = np.concatenate([[False], np.cumsum(rows.any(axis=0)) > 0])     # any_below[n]: some sample has a visible key < n
+        `super_mask`: the same hook for ANY visibility pattern over the K tokens ([K] bool / 0-1, the same for every sample).
+        Which rows a step sees and by which route (slice / gather / in place under key-mask words) is schedule.context_plan's decision.
+        `plan`: the result of `plan_context`, instead of the two -- what a caller that captures this loop in a hipGraph passes, and
+        the way to decode a pattern PER SAMPLE as one batch (`batched=True`)."""
+        B, K = noise.shape[0], int(ehs.shape[1])
+        if plan is not None and (prefix_k is not None or super_mask is not None):
+            raise ValueError("plan is exclusive with prefix_k / super_mask")
+        plan, index, kwords = plan or self.plan_context(dit, k_table, K, prefix_k, super_mask)
+        steps = self.num_timesteps if max_steps is None else min(max_steps, self.num_timesteps)
+        if len(plan.n_live) < steps or (plan.words_rows is not None and plan.words_rows.shape not in ((1, K), (B, K))):
+            raise ValueError(f"plan: expected {steps} steps and words_rows [1 or B, K] = [1 or {B}, {K}]")
         x = noise.to(self.device).float().contiguous()
         hp, wp = x.shape[-2] // 2, x.shape[-1] // 2
-        ctx0 = dit.embed_context(ehs)                                         # step independent
-        tables, vis_pos = None, None
-        if visible is None and super_mask is not None:
-            visible = self.resolve_super_mask(super_mask, ctx0.shape[1])
-        exact_pos = None
-        if visible is not None and dit.gemm == "exact" and not np.array_equal(visible[1], np.arange(len(visible[1]))):
-            # the exact mode keeps every context key at its POSITION in the reference's key sequence (kv blocks of 512, MKL's K-blocks); gathering the
-            # visible tokens of a non-prefix pattern would move them.  So nothing is gathered: the rows 0 .. n_live - 1 stay in place and the exact
-            # attention takes the pattern as one shared row of bit words (device ops on the index made outside any capture: capturable)
-            idx_dev, exact_pos = visible
-            Kc = ctx0.shape[1]
-            kwords = dit.pack_key_mask(torch.zeros(Kc, dtype=torch.int64, device=self.device).scatter_(0, idx_dev, 1)[None])
-        elif visible is not None:
-            idx_dev, vis_pos = visible                                        # device index tensor (made outside any capture), host positions
-            ctx0, tables, _ = dit.gather_context(ctx0, index=idx_dev)
+        ctx0, tables = dit.embed_context(ehs), None                           # step independent
+        if index is not None:
+            ctx0, tables, _ = dit.gather_context(ctx0, index=index)
         cqkv0 = dit.block0_context_qkv(ctx0, tables) if ctx0.shape[1] > 0 else None   # block 0's context QKV is step independent too
-        steps = self.num_timesteps if max_steps is None else min(max_steps, self.num_timesteps)
         for i in range(steps):
-            n_live = int(k_table[i]) + 1                                      # mask = arange(K) <= k  (models_ours.py:353)
-            if prefix_k is not None:
-                n_live = min(n_live, int(prefix_k))
-            if vis_pos is not None:                                           # visible tokens at positions < n_live: a prefix of the gathered list
-                n_live = int(np.searchsorted(vis_pos, n_live, side="left"))
-            if any_below is not None and not any_below[n_live]:               # no sample sees a key at this step: the n_live = 0 route
-                n_live = 0
-            if exact_pos is not None:                                         # rows up to the last visible position below n_live; none: the n_live = 0 route
-                below = int(np.searchsorted(exact_pos, n_live, side="left"))
-                n_live = int(exact_pos[below - 1]) + 1 if below > 0 else 0
+            n_live = int(plan.n_live[i])
             exact = dit.gemm == "exact" and self.t_freq_exact is not None
             tf = (self.t_freq_exact if exact else self.t_freq)[i:i + 1].expand(B, -1).contiguous()
             t_name = float(self.scheduled_t[i])                               # names the embedded timestep (MMDiTGPU._step_modulations)
-            if uncond_scale == 1.0:
-                y = dit.velocity_tokens(x, tf, ctx0, n_live, context_see_xt, cqkv0, tables, t_key=("t", t_name), kmask=kwords)
-                yu = None
-            else:
-                # CFG branch (rectified_flow.py:280-289): the conditional call omits context_see_xt (-> False) and
-                # the unconditional one sees no context token at all
-                y = dit.velocity_tokens(x, tf, ctx0, n_live, False, cqkv0, tables, t_key=("t", t_name), kmask=kwords)
+            # CFG branch (rectified_flow.py:280-289): the conditional call omits context_see_xt (-> False) and the unconditional one
+            # (cfg_inference) sees no context token at all
+            guided = uncond_scale != 1.0
+            y = dit.velocity_tokens(x, tf, ctx0, n_live, context_see_xt and not guided, cqkv0, tables, t_key=("t", t_name), kmask=kwords)
+            yu = None
+            if guided:
                 tfu = (self.t_freq_uncond_exact if exact else self.t_freq_uncond)[i:i + 1].expand(B, -1).contiguous()
-                yu = dit.velocity_tokens(x, tfu, ctx0, 0, False, t_key=("floor", t_name))   # cfg_inference: no context key visible at all
+                yu = dit.velocity_tokens(x, tfu, ctx0, 0, False, t_key=("floor", t_name))
             if self.parameterization == "x0":
                 # the model output is the clean latent: x_prev = v + a_prev (x - v) / a_t  (euler_step, rectified_flow.py:305-307);
                 # the CFG mix rides in the unpatchify kernel, the update is the reference's own chain of fp32 element-wise ops
@@ -292,7 +256,7 @@ class SelftokPipeline():
         self.k_table = self.diti.to_indices(self.flow.t_long)                # k for each of the 50 steps
         self.cond_vary = True
         self.saved_images = 8
-        self._graphs = {}        # (B, latent, steps, scale) -> (hipGraph, static noise, static ehs, static output)
+        self._graphs = {}        # (shapes, steps, scale, gemm, context plan) -> (hipGraph, static noise, static ehs, static output, what the graph reads)
 
     def _say(self, msg):
         if self.verbose:          # the reference prints these progress lines unconditionally (:192,212,223,230,292,299,320)
@@ -423,62 +387,43 @@ class SelftokPipeline():
 
     @torch.no_grad()
     def _sample(self, xt, ehs, max_steps, uncond_scale, use_graph, prefix_k=None, super_mask=None, mask_batched=False):
-        """the 50-step loop, optionally replayed from a hipGraph captured once per (batch, latent size) -- the loop is
-        ~21k kernel launches; at small batch the host cannot issue them as fast as the GPU retires them.
-        `mask_batched`: a [B, K] super_mask with differing rows is decoded as ONE batch (per-sample key bit masks in the joint
-        attention) instead of one sampler call per group of equal rows."""
-        key_mask = km_key = None
-        if super_mask is not None:
-            sm = torch.as_tensor(super_mask).cpu()
-            differ = sm.dim() == 2 and sm.shape[0] == xt.shape[0] and not bool((sm == sm[:1]).all())
-            if differ and mask_batched:
-                if self.model.model.gemm == "exact":
-                    raise NotImplementedError("gemm='exact' decodes one visibility pattern per sampler call: pass super_mask=tokens.suffix_mask(K, m) without "
-                                              "mask_batched (groups of equal pattern), or decode the batch in one pass with gemm='fp32' / 'f16x2'")
-                if prefix_k is not None:
-                    raise ValueError("mask_batched is exclusive with prefix_k")
-                rows = sm.reshape(sm.shape[0], -1).bool().numpy()
-                if rows.shape[1] != self.K:
-                    raise ValueError(f"super_mask has {rows.shape[1]} entries per sample, the tokenizer has K = {self.K} tokens")
-                key_mask = (MMDiTGPU.pack_key_mask(torch.from_numpy(rows).to(self.device)), rows)       # upload + device ops: before any capture
-                import hashlib
-                km_key = hashlib.sha256(rows.tobytes()).hexdigest()
-                super_mask = None
-            elif differ:
-                # a visibility pattern PER SAMPLE (the reference's `mask * super_mask` with a [B, K] tensor, rectified_flow.py:226-227):
-                # samples are independent, so the batch is decoded in groups of equal pattern (a group's context is gathered once)
-                rows = sm.reshape(sm.shape[0], -1).bool().numpy()
-                out = torch.empty(xt.shape, dtype=torch.float32, device=self.device)
-                seen = {}
-                for b in range(rows.shape[0]):
-                    seen.setdefault(rows[b].tobytes(), []).append(b)
-                for idx in seen.values():
-                    sel = torch.as_tensor(idx)
-                    out[sel.to(self.device)] = self._sample(xt[sel], ehs[sel.to(ehs.device)], max_steps, uncond_scale, use_graph, prefix_k, rows[idx[0]])
-                return out
+        """the sampler.  A [B, K] `super_mask` with differing rows (the reference's `mask * super_mask` with a [B, K] tensor, rectified_flow.py:226-227)
+        is decoded as ONE batch with `mask_batched` (per-sample key bit masks in the joint attention), else in groups of equal rows."""
+        B = xt.shape[0]
+        pattern = None if super_mask is None else torch.as_tensor(super_mask).cpu().numpy()
+        batched = bool(mask_batched) and pattern is not None and pattern.ndim == 2 and pattern.shape[0] == B
+        groups = pattern_groups(pattern, B, batched)
+        if groups[0][0] is None:
+            return self._sample_group(xt, ehs, max_steps, uncond_scale, use_graph, prefix_k, groups[0][1], batched)
+        out = torch.empty(xt.shape, dtype=torch.float32, device=self.device)
+        for idx, row in groups:
+            sel = torch.as_tensor(idx)
+            out[sel.to(self.device)] = self._sample_group(xt[sel], ehs[sel.to(ehs.device)], max_steps, uncond_scale, use_graph, prefix_k, row)
+        return out
+
+    def _sample_group(self, xt, ehs, max_steps, uncond_scale, use_graph, prefix_k, pattern, batched=False):
+        """the 50-step loop, optionally replayed from a hipGraph captured once per (batch, latent size, context plan) -- the loop is
+        ~21k kernel launches; at small batch the host cannot issue them as fast as the GPU retires them."""
+        dit = self.model.model
+        plan = self.flow.plan_context(dit, self.k_table, self.K, prefix_k, pattern, batched)       # host read + uploads: before any capture
+        loop = lambda noise, e: self.flow.p_sample_loop(dit, noise, e, self.k_table, context_see_xt=True, uncond_scale=uncond_scale, max_steps=max_steps, plan=plan)
         if not use_graph:
-            return self.flow.p_sample_loop(self.model.model, xt, ehs, self.k_table, context_see_xt=True,
-                                           uncond_scale=uncond_scale, max_steps=max_steps, prefix_k=prefix_k, super_mask=super_mask, key_mask=key_mask)
-        visible = None if super_mask is None else self.flow.resolve_super_mask(super_mask, self.K)     # host read + upload: before the capture
-        sm_key = None if visible is None else visible[1].tobytes()
-        key = (tuple(xt.shape), tuple(ehs.shape), max_steps, float(uncond_scale), self.model.model.gemm, self.model.model.PRESPLIT, self.model.model.SPLITK, prefix_k, sm_key, km_key)
+            return loop(xt, ehs)
+        key = (tuple(xt.shape), tuple(ehs.shape), max_steps, float(uncond_scale), dit.gemm, dit.PRESPLIT, dit.SPLITK, plan[0].key)
         if key not in self._graphs:
             s_noise = torch.empty(xt.shape, dtype=torch.float32, device=self.device)
             s_ehs = torch.empty_like(ehs)
             s_noise.copy_(xt); s_ehs.copy_(ehs)
-            run = lambda: self.flow.p_sample_loop(self.model.model, s_noise, s_ehs, self.k_table, context_see_xt=True,
-                                                  uncond_scale=uncond_scale, max_steps=max_steps, prefix_k=prefix_k, visible=visible, key_mask=key_mask)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):       # warm-up outside capture (hipBLASLt / allocator warm)
-                run()
+                loop(s_noise, s_ehs)
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
-            dit = self.model.model
-            dit._capture_refs = []               # remembered modulations the capture reads: kept alive with the graph (MMDiTGPU._step_modulations)
+            dit._capture_refs = [plan]           # what the capture reads: the plan's uploads, remembered modulations (MMDiTGPU._step_modulations); kept alive with the graph
             try:
                 with torch.cuda.graph(g):
-                    s_out = run()
+                    s_out = loop(s_noise, s_ehs)
                 refs = dit._capture_refs
             finally:
                 dit._capture_refs = None
@@ -506,23 +451,7 @@ class SelftokPipeline():
         `super_mask` (extension): the same hook with any visibility pattern over the K tokens ([K] bool / 0-1 array, or [B, K]: one
         pattern per sample, decoded in groups of equal pattern -- or, with `mask_batched=True`, as one batch)."""
         self._say("Begin decoding.")
-        if prefix_k is not None and not (0 <= int(prefix_k) <= self.K):
-            raise ValueError(f"prefix_k must be in [0, {self.K}]")
-        if ar_partial is not None:
-            if prefix_k is not None or super_mask is not None:
-                raise ValueError("ar_partial is exclusive with prefix_k / super_mask")
-            B_ = int(np.asarray(idx.cpu() if torch.is_tensor(idx) else idx).shape[0])
-            m = np.asarray(ar_partial, dtype=np.int64).reshape(-1)
-            m = np.repeat(m, B_) if m.size == 1 else m
-            if m.size != B_:
-                raise ValueError(f"ar_partial: expected an int or {B_} values, got {m.size}")
-            if m.min() < 0 or m.max() > self.K:
-                raise ValueError(f"ar_partial must be in [0, {self.K}]")
-            sm = tokens.suffix_mask(self.K, m)
-            if bool((m == m[0]).all()):
-                super_mask = sm[0]                                           # the existing uniform route (gathered context)
-            else:
-                super_mask, mask_batched = sm, True
+        super_mask, mask_batched = request_pattern(self.K, int(idx.shape[0]), prefix_k, super_mask, ar_partial, mask_batched)
         outs_q = self._codes(idx)
         B = outs_q.shape[0]
         # t_mapped = timestep_map[0] -> k = K-1 -> enc_mask all true -> encoder_hidden_states = outs_q (:243-252)

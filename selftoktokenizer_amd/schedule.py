@@ -7,10 +7,16 @@ Reproduces bit-for-bit what the reference computes with torch-CPU:
   encoder mask  arange(K) <= k            models_ours.py:345-353   (here: just the visible count k+1)
 The fragile part is float: linspace(1,0,51)*1000 truncates to 459, 399, ... not 460, 400 (SURVEY.md 8a a13/a14);
 tests/test_schedule.py pins this module to tests/golden/schedule.npz (captured from the reference).
+
+`context_plan`: which context rows each sampler step hands to the model, and by which route (tests/test_context_plan_cpu.py).
 """
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
+
 import numpy as np
+
+from . import tokens
 
 f32 = np.float32
 
@@ -84,3 +90,102 @@ def decode_plan(num_steps: int, diti: DiTiCont):
     """-> (FlowSchedule, k[num_steps]) : everything the decode loop needs from the host."""
     flow = FlowSchedule(num_steps)
     return flow, diti.to_indices(flow.t_long)
+
+
+# ---- which context tokens a sampler step may see: mask = (arange(K) <= k) * super_mask  (models_ours.py:353, rectified_flow.py:226-227) ----
+def rows_uniform(rows: np.ndarray) -> bool:
+    return bool((rows == rows[:1]).all())
+
+
+def prefix_lengths(rows: np.ndarray) -> Optional[np.ndarray]:
+    """bool [B, K] -> the visible count of every row if each row is a prefix (arange(K) < count), else None"""
+    cnt = rows.sum(axis=1)
+    return cnt if bool((rows == (np.arange(rows.shape[1])[None] < cnt[:, None])).all()) else None
+
+
+def last_visible(rows: np.ndarray) -> int:
+    """bool [B, K] -> the last position any row sees, + 1 (0: nobody sees anything)"""
+    pos = np.nonzero(rows.any(axis=0))[0]
+    return int(pos[-1]) + 1 if pos.size else 0
+
+
+class ContextPlan(NamedTuple):
+    n_live: np.ndarray                  # int64 [steps]: the context rows handed to the model at each step
+    gather: Optional[np.ndarray]        # sorted positions to gather once (MMDiTGPU.gather_context), or None
+    words_rows: Optional[np.ndarray]    # bool [1, K] / [B, K] to pack into key-mask words (ops.pack_key_mask), or None
+    key: tuple                          # identifies the plan's launches (hipGraph cache)
+
+
+def context_plan(k_table, K: int, steps: int, prefix_k: Optional[int] = None, pattern=None, batched: bool = False,
+                 keep_positions: bool = False) -> ContextPlan:
+    """The visibility of every sampler step, resolved once on the host.  Step i may see token j iff j < limit[i] = min(k_table[i] + 1,
+    prefix_k) and pattern[j]; `pattern`: None, [K], or [B, K] (bool / 0-1).  Routes (arrays of the result are read-only):
+      slice     no pattern: the first n_live = limit rows.
+      gather    one pattern for the batch: its visible rows are gathered once, a step takes the n_live of them below its limit.
+      in place  one NON-prefix pattern with `keep_positions` (gemm='exact' keeps every key at its position in the reference's key
+                sequence -- kv blocks of 512, MKL's K-blocks -- and a gather would move them): rows 0 .. n_live - 1 stay, n_live =
+                the last visible position below the limit, + 1, and the attention takes one shared row of words.
+      batched   differing rows, `batched`: rows stay, n_live = limit (0 when no sample sees a key below it), per-sample words.
+                Without `batched` differing rows are refused: `pattern_groups` splits such a batch first."""
+    limit = np.minimum(np.asarray(k_table[:steps], dtype=np.int64) + 1, K if prefix_k is None else int(prefix_k))
+    n_live, gather, words = limit, None, None
+    rows = None if pattern is None else np.asarray(pattern)
+    if rows is not None and rows.ndim == 2 and not rows_uniform(rows):
+        if not batched:
+            raise NotImplementedError("p_sample_loop takes ONE visibility pattern per call (decode the samples in groups of equal pattern)")
+        if keep_positions:
+            raise NotImplementedError("gemm='exact' decodes one visibility pattern per sampler call: pass super_mask=tokens.suffix_mask(K, m) without "
+                                      "mask_batched (groups of equal pattern), or decode the batch in one pass with gemm='fp32' / 'f16x2'")
+        if prefix_k is not None:
+            raise ValueError("mask_batched is exclusive with prefix_k")
+        if rows.shape[1] != K:
+            raise ValueError(f"super_mask has {rows.shape[1]} entries per sample, the tokenizer has K = {K} tokens")
+        words = rows != 0
+        any_below = np.concatenate([[False], np.cumsum(words.any(axis=0)) > 0])         # any_below[n]: some sample has a visible key < n
+        n_live = np.where(any_below[limit], limit, 0)
+    elif rows is not None:
+        row = (rows[0] if rows.ndim == 2 else rows).reshape(-1) != 0
+        if row.size != K:
+            raise ValueError(f"super_mask has {row.size} entries, the tokenizer has K = {K} tokens")
+        pos = np.nonzero(row)[0].astype(np.int64)
+        below = np.searchsorted(pos, limit, side="left")                                # visible positions below each step's limit
+        if keep_positions and prefix_lengths(row[None]) is None:
+            words, n_live = row[None], np.where(below > 0, pos[np.maximum(below, 1) - 1] + 1, 0)
+        else:
+            gather, n_live = pos, below
+    n_live = n_live.astype(np.int64)
+    for a in (n_live, gather, words):
+        if a is not None:
+            a.setflags(write=False)
+    return ContextPlan(n_live, gather, words, (n_live.tobytes(), gather is not None and gather.tobytes(), words is not None and (words.shape, words.tobytes())))
+
+
+def pattern_groups(pattern, B: int, batched: bool = False):
+    """-> [(sample indices, or None: the whole batch; pattern for `context_plan`)].  A [B, K] pattern with differing rows that is not decoded
+    as one batch becomes one group per distinct row (samples are independent; a group's context is gathered once)."""
+    rows = None if pattern is None else np.asarray(pattern)
+    if rows is None or batched or rows.ndim != 2 or rows.shape[0] != B or rows_uniform(rows):
+        return [(None, rows)]
+    rows, seen = rows.reshape(B, -1) != 0, {}
+    for b in range(B):
+        seen.setdefault(rows[b].tobytes(), []).append(b)
+    return [(idx, rows[idx[0]]) for idx in seen.values()]
+
+
+def request_pattern(K: int, B: int, prefix_k=None, super_mask=None, ar_partial=None, mask_batched: bool = False):
+    """the visibility arguments of `SelftokPipeline.decoding`, checked -> (pattern, mask_batched).  `ar_partial` (an int, or one value per
+    sample) is the pattern tokens.suffix_mask(K, m): one [K] row when every m is the same, else [B, K] decoded as one batch."""
+    if prefix_k is not None and not (0 <= int(prefix_k) <= K):
+        raise ValueError(f"prefix_k must be in [0, {K}]")
+    if ar_partial is None:
+        return super_mask, mask_batched
+    if prefix_k is not None or super_mask is not None:
+        raise ValueError("ar_partial is exclusive with prefix_k / super_mask")
+    m = np.asarray(ar_partial, dtype=np.int64).reshape(-1)
+    m = np.repeat(m, B) if m.size == 1 else m
+    if m.size != B:
+        raise ValueError(f"ar_partial: expected an int or {B} values, got {m.size}")
+    if m.min() < 0 or m.max() > K:
+        raise ValueError(f"ar_partial must be in [0, {K}]")
+    sm = tokens.suffix_mask(K, m)
+    return (sm[0], mask_batched) if bool((m == m[0]).all()) else (sm, True)
