@@ -67,6 +67,23 @@ int selftok_img_resize_crop_norm_u8(const unsigned char* packed, size_t packed_b
  * float -> uint8 conversion of NaN is undefined).  B * H * W < 2^31. */
 int selftok_img_to_u8(const void* img, int in_bf16, unsigned char* out, int B, int H, int W, hipStream_t stream);
 
+/* ---- device image metrics: per-image SSIM and mean squared error in one pass ----------------------------
+ * recon [B, 3, H, W] in [0, 1] (recon_bf16 != 0: bf16, else fp32) against orig [B, 3, H, W] (orig_bf16 likewise), both contiguous ->
+ * out [B][2] fp64 on the device: {mean SSIM, MSE} of each image.  orig_signed != 0: the original is in [-1, 1] and becomes
+ * o = (float32(v) + 1) / 2 in fp32 (evaluate.psnr_each's expression), else o = float32(v).
+ * SSIM: Wang et al., the 11 x 11 separable window whose 11 fp64 weights the caller passes in `window11_host` (host memory, copied into
+ * the launch; normally the normalised Gaussian of sigma 1.5), "valid" windows only ((H - 10) x (W - 10) of them per channel, no padding),
+ * population moments, C1 = 0.01^2, C2 = 0.03^2 (data range 1), every operation in fp64 and rounded on its own, the fp64 mean over the three
+ * channels and all windows.  MSE: d = float32(recon) - o and d * d in fp32, summed in fp64, divided by 3 * H * W; PSNR is the caller's
+ * 10 * log10(1 / MSE).  quantize != 0: both inputs first become the bytes of selftok_img_to_u8 (the reconstruction in its own type, o in
+ * fp32), SSIM is taken on byte / 255.0 in fp64 and MSE is the exact integer sum of (bx - by)^2 divided by 65025 * 3 * H * W.
+ * No atomics: out[b] is a function of image b alone, bit-identical from run to run and for any batch around it.
+ * Limits: B >= 1, H, W >= 11, B * 3 * H * W < 2^31.  The workspace (one pair of partial sums per tile) is sized by the query; 0 with
+ * selftok_last_error set on a refused shape. */
+size_t selftok_img_metrics_workspace_bytes(int B, int H, int W);
+int selftok_img_metrics(const void* recon, int recon_bf16, const void* orig, int orig_bf16, int orig_signed, int quantize, const double* window11_host, double* out,
+                        void* workspace, size_t workspace_bytes, int B, int H, int W, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,12 +39,46 @@ def psnr_each(recon: torch.Tensor, original: torch.Tensor) -> np.ndarray:
     return (10.0 * torch.log10(1.0 / mse)).numpy()
 
 
+SSIM_DEFINITION = {"window": 11, "sigma": 1.5, "K1": 0.01, "K2": 0.03, "data_range": 1.0, "covariance": "population", "region": "valid"}
+
+
+def ssim_window() -> np.ndarray:
+    """the 11 fp64 weights of the SSIM window: g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)), normalised to sum 1 -- the one place they are computed (the device entry
+    takes them as an argument, the emulation of the tests calls this)"""
+    i = np.arange(SSIM_DEFINITION["window"], dtype=np.float64) - (SSIM_DEFINITION["window"] // 2)
+    g = np.exp(-(i * i) / (2.0 * SSIM_DEFINITION["sigma"] ** 2))
+    return np.ascontiguousarray(g / g.sum())
+
+
+def psnr_of_mse(mse: np.ndarray) -> np.ndarray:
+    with np.errstate(divide="ignore"):
+        return 10.0 * np.log10(1.0 / np.asarray(mse, dtype=np.float64))
+
+
+def metrics_each(recon: torch.Tensor, original: torch.Tensor, quantize: bool = False):
+    """recon [B,3,H,W] in [0,1], original [B,3,H,W] in [-1,1], both on the GPU (bf16 or fp32) -> (ssim [B], psnr_dB [B]) as numpy fp64, from ONE device call
+    (ops.image_metrics: SSIM as SSIM_DEFINITION says, the MSE with psnr_each's operations).  `quantize`: on the bytes save_image would write."""
+    from . import ops
+    m = ops.image_metrics(recon.detach(), original.detach(), original_signed=True, quantize=quantize).cpu().numpy()
+    return m[:, 0].copy(), psnr_of_mse(m[:, 1])
+
+
 def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int, batch: int = 64, decoders: Sequence[str] = ("diffusion",),
-             noise_fn: Optional[Callable[[int, int], torch.Tensor]] = None, seed: Optional[int] = 1234, renderer_pipe=None, verbose: bool = False) -> Dict:
+             noise_fn: Optional[Callable[[int, int], torch.Tensor]] = None, seed: Optional[int] = 1234, renderer_pipe=None, verbose: bool = False,
+             metrics: Sequence[str] = ("psnr",), metrics_u8: bool = False) -> Dict:
     """PSNR of `n_images` images through `pipe` (and `renderer_pipe` for the one-step decoder), this rank's contiguous shard of them
     (dist.shard_range) in batches of `batch`; per-image values are gathered to every rank (one all_gather_into_tensor per decoder at the end).
     load_batch(lo, hi) -> float tensor [hi-lo, 3, H, W] in [-1, 1] (host or device).  noise_fn(lo, hi) -> [hi-lo, 16, h, w] replaces the
-    reference's `torch.randn` draw (global CPU generator, seeded here with `seed` + rank when given)."""
+    reference's `torch.randn` draw (global CPU generator, seeded here with `seed` + rank when given).
+    metrics (extension): ("psnr",) is the host route above.  With "ssim" in it both figures come from one device call per batch (ops.image_metrics, no host
+    copy of the images, one read of the [n, 2] results at the end): every decoder's dict gains `ssim_mean` / `ssim_each` and the result says which SSIM it is
+    (`metric_definition`).  metrics_u8: take both on the bytes `save_image` would write (needs "ssim": the host route has no such mode)."""
+    bad = [m for m in metrics if m not in ("psnr", "ssim")]
+    if bad or not metrics:
+        raise ValueError(f"metrics {tuple(metrics)!r}: expected a non-empty subset of ('psnr', 'ssim')")
+    on_device = "ssim" in metrics
+    if metrics_u8 and not on_device:
+        raise ValueError("metrics_u8 needs 'ssim' in `metrics` (the device route); the host PSNR route is the float one")
     world, rank = D.world_size(), D.rank()       # the dist module's view: sharding and the gather below must agree (ADVICE r5)
     lo, hi = D.shard_range(n_images, rank, world)
     counts = [D.shard_range(n_images, r, world)[1] - D.shard_range(n_images, r, world)[0] for r in range(world)]
@@ -66,14 +100,28 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
                 rec = (renderer_pipe or pipe).decoding_with_renderer(ids, device=pipe.device)
             else:
                 raise ValueError(f"decoder {d!r}: expected 'diffusion' or 'renderer'")
-            vals[d].append(psnr_each(rec, imgs))
+            if on_device:
+                from . import ops
+                vals[d].append(ops.image_metrics(rec.detach(), imgs, original_signed=True, quantize=metrics_u8))      # [b, 2] fp64, stays on the device
+            else:
+                vals[d].append(psnr_each(rec, imgs))
         if verbose and rank == 0:
-            print(f"[eval] images {b0}..{b1 - 1} of shard {lo}..{hi - 1}: " + ", ".join(f"{d} {np.concatenate(vals[d]).mean():.4f} dB so far" for d in decoders), flush=True)
+            so_far = (lambda d: float(psnr_of_mse(torch.cat(vals[d])[:, 1].cpu().numpy()).mean())) if on_device else (lambda d: np.concatenate(vals[d]).mean())
+            print(f"[eval] images {b0}..{b1 - 1} of shard {lo}..{hi - 1}: " + ", ".join(f"{d} {so_far(d):.4f} dB so far" for d in decoders), flush=True)
     out = {"images": int(n_images), "ranks": world, "batch": int(batch), "shard": [int(lo), int(hi)]}
     for d in decoders:
+        if on_device:
+            mine = torch.cat(vals[d]) if vals[d] else torch.zeros(0, 2, dtype=torch.float64, device=pipe.device)
+            allv = D.all_gather_rows(mine, counts).cpu().numpy()
+            ssim, psnr = allv[:, 0], psnr_of_mse(allv[:, 1])
+            out[d] = {"psnr_mean_dB": float(psnr.mean()) if psnr.size else float("nan"), "psnr_each_dB": [round(float(v), 6) for v in psnr],
+                      "ssim_mean": float(ssim.mean()) if ssim.size else float("nan"), "ssim_each": [round(float(v), 9) for v in ssim]}
+            continue
         mine = torch.from_numpy(np.concatenate(vals[d]) if vals[d] else np.zeros(0)).to(torch.float64)
         allv = D.all_gather_rows(mine.to(pipe.device), counts).cpu().numpy()      # returns `mine` when there is no exchange to perform
         out[d] = {"psnr_mean_dB": float(allv.mean()) if allv.size else float("nan"), "psnr_each_dB": [round(float(v), 6) for v in allv]}
+    if on_device:
+        out["metric_definition"] = dict(SSIM_DEFINITION, on="u8" if metrics_u8 else "float")
     out["token_ids_first_image"] = ids_all[0][0, :8].tolist() if ids_all else []
     return out
 

@@ -1067,3 +1067,41 @@ def image_to_u8(img: torch.Tensor) -> torch.Tensor:
     out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=img.device)
     _lib.check(_lib.load().selftok_img_to_u8(_p(img), int(img.dtype == torch.bfloat16), _p(out), B, H, W, _stream()), "selftok_img_to_u8")
     return out
+
+
+# ---- device image metrics (csrc/image_metrics.hip, include/selftok_hip_ext.h) ----
+_IMG_METRICS_WS = {}     # (device index, stream handle) -> workspace tensors, largest last (the `_LINEAR_WS` rules: one stream's calls are ordered, outgrown tensors stay
+                         # referenced because a captured hipGraph may replay on them)
+
+
+def _img_metrics_ws(device, nbytes: int):
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream))
+    held = _IMG_METRICS_WS.setdefault(key, [])
+    if not held or held[-1].numel() < nbytes:
+        held.append(torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device))
+    return held[-1]
+
+
+def image_metrics(recon: torch.Tensor, original: torch.Tensor, original_signed: bool = True, quantize: bool = False) -> torch.Tensor:
+    """recon [B, 3, H, W] in [0, 1] against original [B, 3, H, W] (in [-1, 1] when `original_signed`, else in [0, 1]), bf16 or fp32 each -> float64 [B, 2] on the
+    device: {mean SSIM, MSE} per image (11 x 11 Gaussian window of sigma 1.5 = evaluate.ssim_window(), valid windows, population moments, fp64; the MSE with
+    evaluate.psnr_each's operations).  `quantize`: on the bytes `image_to_u8` would write for both.  No host synchronisation; H, W >= 11."""
+    _need_cuda(recon, original)
+    for name, t in (("recon", recon), ("original", original)):
+        if t.dtype not in (torch.bfloat16, torch.float32):
+            raise _lib.SelftokHipError(f"image_metrics: `{name}` dtype {t.dtype}: expected bfloat16 or float32")
+    if recon.dim() != 4 or recon.shape[1] != 3 or tuple(original.shape) != tuple(recon.shape):
+        raise _lib.SelftokHipError(f"image_metrics: expected two [B, 3, H, W] tensors of one shape, got {tuple(recon.shape)} and {tuple(original.shape)}")
+    from .evaluate import ssim_window
+    win = ssim_window()
+    recon, original = recon.contiguous(), original.contiguous()
+    B, _, H, W = recon.shape
+    lib = _lib.load()
+    nbytes = lib.selftok_img_metrics_workspace_bytes(B, H, W)
+    if nbytes == 0:
+        _lib.check(-1, "selftok_img_metrics_workspace_bytes")
+    ws = _img_metrics_ws(recon.device, nbytes)
+    out = torch.empty(B, 2, dtype=torch.float64, device=recon.device)
+    _lib.check(lib.selftok_img_metrics(_p(recon), int(recon.dtype == torch.bfloat16), _p(original), int(original.dtype == torch.bfloat16), int(bool(original_signed)),
+                                       int(bool(quantize)), win.ctypes.data, _p(out), _p(ws), ws.numel(), B, H, W, _stream()), "selftok_img_metrics")
+    return out

@@ -5,7 +5,8 @@ README.md:89-94; see selftoktokenizer_amd/evaluate.py).  Sharded over ranks when
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/eval_psnr.py --images <dir> ... --renderer-yml configs/renderer/renderer-eval.yml --renderer-pretrained renderer_512_ckpt.pth
     python tools/eval_psnr.py --synthetic 16          # no checkpoint reachable: hash-generated weights / images / noise = the reference pipeline's golden run
 
-Prints ONE JSON line on rank 0: per-image and mean PSNR for the 50-step `decoding` and, when a renderer checkpoint is given, `decoding_with_renderer`."""
+Prints ONE JSON line on rank 0: per-image and mean PSNR for the 50-step `decoding` and, when a renderer checkpoint is given, `decoding_with_renderer`;
+with --ssim also `ssim_mean` / `ssim_each` (the SSIM column of the reference's results table), computed on the GPU together with the PSNR."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,6 +29,8 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--seed", type=int, default=1234)
 ap.add_argument("--gemm", default=None, choices=["fp32", "f16x2", "exact"], help="exact: every operation in the reference's torch-CPU order (bit-equal pixels, the parity mode)")
 ap.add_argument("--device-io", action="store_true", help="resize / crop / normalise the decoded files on the GPU (preprocess.DeviceLoader): the same values, bit for bit")
+ap.add_argument("--ssim", action="store_true", help="also the SSIM of every image (11 x 11 Gaussian window, sigma 1.5, valid region); both figures then come from one device call per batch")
+ap.add_argument("--metrics-u8", action="store_true", help="with --ssim: take PSNR and SSIM on the uint8 bytes save_image would write instead of the float tensors")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file (rank 0)")
 a = ap.parse_args()
 
@@ -58,13 +61,19 @@ else:
         paths = paths[:a.limit]
     assert paths, f"no image files under {a.images}"
     n, load, noise, src = len(paths), E.folder_loader(paths, a.data_size, device=dev if a.device_io else None), None, f"{len(paths)} files under {a.images}"
-res = E.evaluate(pipe, load, n, batch=a.batch, decoders=decoders, noise_fn=noise, seed=a.seed, renderer_pipe=rpipe, verbose=True)
+if a.metrics_u8 and not a.ssim:
+    ap.error("--metrics-u8 needs --ssim (the device metrics route)")
+mkw = dict(metrics=("psnr", "ssim"), metrics_u8=a.metrics_u8) if a.ssim else {}
+res = E.evaluate(pipe, load, n, batch=a.batch, decoders=decoders, noise_fn=noise, seed=a.seed, renderer_pipe=rpipe, verbose=True, **mkw)
 D.barrier()
 if rank == 0:
-    line = {"tool": "eval_psnr", "source": src, "data_size": a.data_size, "tokens": K, "gemm": pipe.model.model.gemm, "vae": pipe.vae.mode, "encoder": pipe.model.encoder.mode,
+    line = {"tool": "eval_psnr", "source": src, "data_size": a.data_size, "tokens": K, "gemm": pipe.model.model.gemm, "vae": pipe.vae.mode, "vae_decode": pipe.vae.decode_mode, "encoder": pipe.model.encoder.mode,
             "checkpoint": a.pretrained or "synthetic (hash-generated)", "renderer_checkpoint": a.renderer_pretrained, **res,
             "readme_reference_dB": {"tokenizer_512_ckpt": 21.86, "renderer_512_ckpt": 24.14, "tokenizer_1024_ckpt": 23.06, "renderer_1024_ckpt": 26.30,
                                     "note": "README.md:89-94 (256 x 256), needs the published weights"}}
+    if a.ssim:                                   # BASELINE.md rows 17-18; the reference's table does not say which decoder produced them
+        line["paper_reference_ssim"] = {"512": 0.709, "1024": 0.805,
+                                        "note": "assets/results_table.PNG (README.md:61-65): ImageNet-val 50k at 256 x 256, decoder and SSIM variant not stated; needs the published weights"}
     print(json.dumps(line), flush=True)
     if a.out:
         open(a.out, "w").write(json.dumps(line) + "\n")
