@@ -84,6 +84,24 @@ size_t selftok_img_metrics_workspace_bytes(int B, int H, int W);
 int selftok_img_metrics(const void* recon, int recon_bf16, const void* orig, int orig_bf16, int orig_signed, int quantize, const double* window11_host, double* out,
                         void* workspace, size_t workspace_bytes, int B, int H, int W, hipStream_t stream);
 
+/* ---- VQ lookup: the k best codes of every row with their exact scores ------------------------------------
+ * z [N, 16] fp32 and `packed` (selftok_vq_pack_codebook) as for selftok_vq_encode_packed_f32 -> ids [N, k] (int64, or int32 with
+ * SELFTOK_IDS_I32) and scores [N, k] fp32.  With x = l2norm16(z[n]) (SELFTOK_PRENORMED: x = z[n]) and s[c] the canonical k-ordered fp32
+ * FMA chain of the argmax entries, row n receives the first k codes in this order -- defined here, NOT torch.topk's, which promises none
+ * among ties:
+ *   score descending; equal scores (-0.0 == +0.0) by ascending code index; NaN scores before every number, among themselves by
+ *   ascending index.  A zero score is written as +0.0 and a NaN score as the quiet NaN 0x7FC00000, as `best` is.
+ * Column 0 is bit for bit the (ids, best) of selftok_vq_encode_packed_f32.  The [N, C] score matrix is never materialised.
+ * flags: SELFTOK_IDS_I32, SELFTOK_PRENORMED, and the launch-shape overrides SELFTOK_VQ_RT(1|2|4) / SELFTOK_VQ_SPLIT(n), on which the
+ * outputs never depend (a split count above min(64, C / 32) is ignored).  1 <= k <= 8, D == 16, C % 32 == 0: anything else returns
+ * SELFTOK_EINVAL with a message in selftok_last_error and launches nothing.  N == 0 returns 0 and writes nothing.
+ * Workspace: min(64, C / 32) * max(N, 1) * kpad * 8 bytes, kpad = k rounded up to 1, 2, 4 or 8 -- one sorted list of kpad 64-bit keys
+ * (orderable(score) << 32 | 0xFFFFFFFF - code) per code split and row; it does not grow with N * C.  The query returns 0 with
+ * selftok_last_error set for k, C or N out of range. */
+size_t selftok_vq_topk_workspace_bytes(int N, int C, int k);
+int selftok_vq_topk_packed_f32(const float* z, const float* packed, void* ids, float* scores, void* workspace,
+                               int N, int C, int D, int k, int flags, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

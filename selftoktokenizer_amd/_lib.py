@@ -91,6 +91,8 @@ EXT_SIGNATURES = {
     "selftok_img_to_u8": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
     "selftok_img_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "selftok_img_metrics": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "selftok_vq_topk_workspace_bytes": (_sz, [_i, _i, _i]),
+    "selftok_vq_topk_packed_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
 

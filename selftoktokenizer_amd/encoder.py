@@ -237,6 +237,12 @@ class QformerEncoderGPU(ModuleSurface):
         return self.lin("encoder.quantizer.project_in", self._pre_norm(q))
 
     @torch.no_grad()
+    def topk(self, x: torch.Tensor, k: int = 2):
+        """(extension) x0 -> (ids [B,K,k] int64, scores [B,K,k] fp32): the k best codes of every token and their canonical scores
+        (ops.vq_topk) from the same pre-quantizer features `__call__` quantizes; ids[..., 0] are its token ids."""
+        return ops.vq_topk(self.features(x), self.codebook_packed, k)
+
+    @torch.no_grad()
     def __call__(self, x=None, hidden_states=None, d=None, kwargs=None):
         """`outs_q, indices = encoder(x_0, d=None)` (models_ours.py:204-251).  With d given, returns the
         7-tuple of the reference (only `attn_mask` is ever consumed, rectified_flow.py:215)."""

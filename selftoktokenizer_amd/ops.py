@@ -113,6 +113,28 @@ def vq_encode(z: torch.Tensor, codebook: torch.Tensor, *, packed: bool = False, 
     return ids
 
 
+def vq_topk(z: torch.Tensor, packed_codebook: torch.Tensor, k: int, ids_dtype=torch.int64, prenormed: bool = False, *, rt: int = 0, split: int = 0):
+    """z [...,16] fp32 (pre-norm), packed code book (vq_pack_codebook) -> (ids [...,k], scores [...,k] fp32): the k <= 8 best codes of every
+    row and their canonical scores, ordered by score descending, equal scores by ascending index, NaN scores first (the order is defined
+    by include/selftok_hip_ext.h, not torch.topk's).  [..., 0] is bit for bit vq_encode(..., return_best=True).  The [N, C] score matrix is
+    never materialised.  rt / split: launch-shape overrides (SELFTOK_VQ_RT / SELFTOK_VQ_SPLIT; 0 = automatic), never visible in the result."""
+    _need_cuda(z, packed_codebook)
+    if ids_dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"ids_dtype must be torch.int64 or torch.int32, got {ids_dtype}")
+    lib = _lib.load()
+    k = int(k)
+    zz = z.contiguous().float().reshape(-1, z.shape[-1])
+    N, D = zz.shape
+    C = packed_codes(packed_codebook, D)
+    ids = torch.empty((N, max(k, 0)), dtype=ids_dtype, device=z.device)
+    scores = torch.empty((N, max(k, 0)), dtype=torch.float32, device=z.device)
+    ws = torch.empty(lib.selftok_vq_topk_workspace_bytes(N, C, k), dtype=torch.uint8, device=z.device)
+    flags = (IDS_I32 if ids_dtype == torch.int32 else 0) | (PRENORMED if prenormed else 0) | ((rt & 0xF) << 8) | ((split & 0xFF) << 16)
+    _lib.check(lib.selftok_vq_topk_packed_f32(_p(zz), _p(packed_codebook), _p(ids), _p(scores), _p(ws), N, C, D, k, flags, _stream()),
+               "selftok_vq_topk_packed_f32")
+    return ids.reshape(z.shape[:-1] + (k,)), scores.reshape(z.shape[:-1] + (k,))
+
+
 def vq_ema_accumulate(z: torch.Tensor, ids: torch.Tensor, C: int, prenormed: bool = False):
     """(bins [C], embed_sum [C,16]) of one batch: bins[c] = #rows with id c, embed_sum[c] = sum of their l2-normalised features
     (the reference's one-hot contractions, vector_quantize_pytorch.py:587-593)."""

@@ -281,6 +281,14 @@ class SelftokPipeline():
 
     @_on_own_device
     @torch.no_grad()
+    def encoding_topk(self, images, k: int = 2, device=None):
+        """(extension) `encoding` with the runners-up: (ids [B,K,k] int64, scores [B,K,k] fp32), the k <= 8 best codes of every token and
+        their exact cosine scores, best first (ties by ascending id).  ids[..., 0] equals encoding(images); tokens.margins(scores) is the
+        top-1 / top-2 gap that tells which tokens are near-ties."""
+        return self.model.encoder.topk(self.encode_latents(images), k)
+
+    @_on_own_device
+    @torch.no_grad()
     def preprocess_u8(self, images, dtype=None) -> torch.Tensor:
         """(extension) uint8 RGB HWC images -- a list of arrays of ANY sizes, or one uint8 tensor [B, H, W, 3] (host or device) -> the
         [B, 3, datasize, datasize] batch `encoding` takes, on the device: Resize(datasize) -> CenterCrop(datasize) -> NormalizeToTensor of
@@ -300,10 +308,12 @@ class SelftokPipeline():
             loaders[dtype] = DeviceLoader(int(self.datasize), self.device, dtype=dtype)
         return loaders[dtype].load(images)
 
-    def encoding_u8(self, images, device=None):
+    def encoding_u8(self, images, device=None, topk: int = 0):
         """(extension) `encoding` from 8-bit pixels: equal to encoding(torch.stack([load_image-equivalent of each image])) -- same bf16 tensor
-        into the VAE, same token ids -- without the per-image PIL resize, fp32 tensors and pageable copy on the host."""
-        return self.encoding(self.preprocess_u8(images), device=device)
+        into the VAE, same token ids -- without the per-image PIL resize, fp32 tensors and pageable copy on the host.  topk = k > 0: the (ids, scores)
+        of `encoding_topk(..., k)` instead."""
+        x = self.preprocess_u8(images)
+        return self.encoding_topk(x, k=topk, device=device) if topk else self.encoding(x, device=device)
 
     @_on_own_device
     @torch.no_grad()

@@ -111,3 +111,12 @@ def prefix_mask(K: int, k) -> np.ndarray:
     """visibility mask of a partial decode that uses only tokens 0..k (reference get_encoder_mask, models_ours.py:345-353)"""
     k = np.asarray(k).reshape(-1, 1)
     return np.arange(K)[None, :] <= k
+
+
+def margins(scores):
+    """scores [..., k >= 2] of `SelftokPipeline.encoding_topk` / `ops.vq_topk` -> scores[..., 0] - scores[..., 1], the amount by which every
+    token's id won over the runner-up.  A small margin marks a near-tie: a token that another VAE mode, batch size or GPU may move.
+    numpy in, numpy out; a torch tensor gives a torch tensor."""
+    if scores.shape[-1] < 2:
+        raise ValueError("margins need the two best scores of every token (k >= 2)")
+    return scores[..., 0] - scores[..., 1]

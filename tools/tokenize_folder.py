@@ -5,7 +5,9 @@ GPU (csrc/image_io.hip, the reference's PIL arithmetic bit for bit) -> `encoding
     python tools/tokenize_folder.py --synthetic 256 --out /tmp/ids          # hash-generated weights and mixed-size uint8 images
 
 Every rank writes <out>.rank<r>.npy (int64 [n, K], what the reference script saves; --uint16 for the compact wire format) and rank 0 prints
-ONE JSON line: images/s and where the time went (host decode, pack, H2D copy, resize kernels, encode)."""
+ONE JSON line: images/s and where the time went (host decode, pack, H2D copy, resize kernels, encode).  --topk k also writes
+<out>.rank<r>.topk.npz (`ids` uint16 [n, K, k]: the k best codes of every token, best first; `scores` fp32 [n, K, k]: their exact cosine scores)
+and, for k >= 2, adds the near-tie census of the top-1 / top-2 margins to the JSON line; the .npy is the same bytes with and without it."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -28,8 +30,11 @@ ap.add_argument("--workers", type=int, default=8, help="host decode threads (at 
 ap.add_argument("--encoder-mode", default=None, choices=["exact", "fast"])
 ap.add_argument("--vae-mode", default=None, choices=["exact", "parity", "fast", "miopen"])
 ap.add_argument("--uint16", action="store_true", help="write tokens.to_uint16 ids instead of the reference's int64")
+ap.add_argument("--topk", type=int, default=0, help="k in 1..8: also keep every token's k best codes and their scores (SelftokPipeline.encoding_topk); the margin census needs k >= 2")
 ap.add_argument("--out", default=None, help="prefix of the id files; nothing is written without it")
 a = ap.parse_args()
+if not 0 <= a.topk <= 8:
+    ap.error("--topk k: 1 <= k <= 8")
 
 rank, world, local = D.init_from_env()
 torch.cuda.set_device(local)
@@ -56,17 +61,24 @@ else:
 
 loader = preprocess.DeviceLoader(a.data_size, dev, dtype=torch.bfloat16, workers=a.workers)
 loader.timing = True
+topk_ids, topk_scores = [], []
 ids, split, marks = [], {"host_decode_s": 0.0, "pack_s": 0.0, "h2d_ms": 0.0, "resize_kernels_ms": 0.0, "encode_ms": 0.0}, []
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for batch in loader.batches(items, a.batch):
     ev, lt = loader.last_events, loader.last_times
     e3 = torch.cuda.Event(enable_timing=True)
-    tok = pipe.encoding(batch, device=dev)
+    if a.topk:
+        tk_ids, tk_scores = pipe.encoding_topk(batch, k=a.topk, device=dev)
+        tok = tk_ids[..., 0]
+    else:
+        tok = pipe.encoding(batch, device=dev)
     e3.record()
     marks.append(ev + (e3,))
     split["host_decode_s"] += lt["decode_s"]; split["pack_s"] += lt["pack_s"]
     ids.append(tok.cpu().numpy())
+    if a.topk:
+        topk_ids.append(tk_ids.cpu().numpy()); topk_scores.append(tk_scores.cpu().numpy())
 torch.cuda.synchronize()
 wall = time.perf_counter() - t0
 for e0, e1, e2, e3 in marks:
@@ -76,6 +88,17 @@ ids = np.concatenate(ids) if ids else np.zeros((0, K), np.int64)
 if a.out:
     f = f"{a.out}.rank{rank}.npy"
     np.save(f, tokens.to_uint16(ids)) if a.uint16 else tokens.save_reference_npy(f, ids)
+extra = {}
+if a.topk:
+    topk_ids = np.concatenate(topk_ids) if topk_ids else np.zeros((0, K, a.topk), np.int64)
+    topk_scores = np.concatenate(topk_scores) if topk_scores else np.zeros((0, K, a.topk), np.float32)
+    if a.out:
+        np.savez(f"{a.out}.rank{rank}.topk.npz", ids=tokens.to_uint16(topk_ids), scores=topk_scores)
+    extra = {"topk": a.topk}
+    if a.topk >= 2:                  # the margin needs the runner-up
+        m = tokens.margins(topk_scores)
+        extra.update({"rank0_margin_below_1e-5": int((m < 1e-5).sum()), "rank0_margin_below_1e-4": int((m < 1e-4).sum()),
+                      "rank0_min_margin": float(m.min()) if m.size else None})
 slowest = D.max_over_ranks(wall, dev)
 D.barrier()
 if rank == 0:
@@ -83,5 +106,6 @@ if rank == 0:
                       "data_size": a.data_size, "vae": pipe.vae.mode, "encoder": pipe.model.encoder.mode, "wall_s": round(slowest, 4),
                       "images_per_s": round(n / slowest, 2) if slowest > 0 else None,
                       "rank0_split": {k: round(v, 4) for k, v in split.items()}, "rank0_shard": [lo, hi],
+                      **extra,
                       "note": "host decode / pack of batch i + 1 overlap the GPU work of batch i, so the parts do not add up to wall_s"}), flush=True)
 D.shutdown()
