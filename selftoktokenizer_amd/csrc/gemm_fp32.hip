@@ -81,7 +81,7 @@ struct SgArgs {
     const float* bias;
     const float* res; long ldr; int res_mod;    // y = res[row(m, res_mod)][n] + (gate ? gate * y : y); row(m, d) = m % d (d > 0), m / -d (d < 0), m (0)
     const float* gate; long ldg; int gate_mod;
-    float* ws;                                  // tail planes: [xcd][tail tile][plane][128][128]
+    float* ws;                                  // tail planes: [xcd][tail tile][plane][256][128] (SG_PLANE floats each)
     int M, N, K;
     int gelu, bias_last;
     int mt, nt, tiles, per;                     // tile grid; per = ceil(tiles / 8) list entries per XCD

@@ -605,7 +605,7 @@ def _linear_f32(flags, exact_note):
         x = f32(r.standard_normal((M, K))); w = f32(r.standard_normal((N, K)) / np.sqrt(K)); b = f32(r.standard_normal(N))
         res = f32(r.standard_normal((M, N))); gate = f32(r.standard_normal((T, 2 * N)))
         out = alloc(np.zeros((M, N), np.float32))
-        ws = alloc(np.zeros(8 * 1 * 8 * 128 * 128 * 4, np.uint8))            # >= selftok_linear_f32_workspace_bytes(300, 256, 1536, .): 8 XCDs x 1 tail tile x (4 K-blocks | 8 units) planes
+        ws = alloc(np.zeros(8 * 1 * 8 * 128 * 128 * 4, np.uint8))            # 8 XCDs x 1 tail tile x 4 planes of 256 x 128 floats: what MKL order's 4 K-blocks take; free order plans within it (split 4 instead of 8)
         return "selftok_linear_f32", [alloc(x).ptr, K, alloc(w).ptr, alloc(b).ptr, alloc(res).ptr, N, 0, alloc(gate).ptr + 4 * N, 2 * N, T, out.ptr, N,
                                       M, N, K, flags, ws.ptr, 8 * 8 * 128 * 128 * 4, None], dict(out=out)
     return fn

@@ -1,6 +1,7 @@
 """-m gpu: csrc/gemm_fp32.hip (`selftok_linear_f32`, round 6) -- the LDS-DMA staged fp32-MFMA Linear.
 MKL order: bit-equal to the CPU oracle (oracle/encoder_exact.c: torch-CPU's own F.linear bits) and to the round-5 kernel (`ex_linear(kernel='xe')`) at the MMDiT's full
-shapes, with every epilogue, ragged row counts, and the tail round both planned and forced.  Free order: error against fp64 not above the fp32 library GEMM's."""
+shapes, with every epilogue, ragged row counts, and the tail round both planned and forced.  Free order: error against fp64 not above the fp32 library GEMM's.
+The small shapes at which the tile list, the tail split, the pipeline depth and the strides change path: tests/test_gemm_fp32_edges_gpu.py (cases: tests/gemm_fp32_cases.py)."""
 import numpy as np
 import pytest
 import torch
