@@ -102,6 +102,25 @@ size_t selftok_vq_topk_workspace_bytes(int N, int C, int k);
 int selftok_vq_topk_packed_f32(const float* z, const float* packed, void* ids, float* scores, void* workspace,
                                int N, int C, int D, int k, int flags, hipStream_t stream);
 
+/* ---- single-pass fp16 Linear on the split planes (the "f16" GEMM mode) ---------------------------------
+ * The two pre-split f16x2 Linears of selftok_hip.h (selftok_linear_f16x2_split, selftok_linear_f16x2_split_residual) with both
+ * LOW planes taken as zero:
+ *     out = act(fp16(A) fp16(W)^T + bias),  fp16-rounded operands, fp32 accumulation, one matrix instruction per product
+ * -- a LOSSY mode (11 significand bits per operand), not fp32-equivalent.  Same argument lists, same inputs: `a_blk` is a split
+ * activation [M, K] and `packed` the image of selftok_linear_f16x2_pack_weight; only their hi planes are read (the lo planes may
+ * hold anything).  Every output is the ascending-k chain of 16-deep steps of the f16x2 kernel's high accumulator and the epilogue
+ * is that kernel's with lo = 0, so on operands that are exactly representable in fp16 the results equal the f16x2 entries'.
+ * flags: SELFTOK_LINEAR_GELU.  Output: fp32 `out` (row stride ldo, out_blk = NULL) or a split activation [M, N] with BOTH planes
+ * (out = NULL).  The residual entry computes resid + gate * (A W^T + bias) as selftok_linear_f16x2_split_residual does (gate NULL,
+ * per-sample or per-token table).  overflow bit 0 is OR-ed for a non-finite output (an |activation| >= 65504 is one).
+ * Refusals as the f16x2 entries: N % 128, K % 32, null / unaligned pointers, bad strides -> SELFTOK_EINVAL; M == 0 returns 0 without
+ * a launch.  There is no split-K variant: small row counts belong on selftok_linear_f16x2_split_k. */
+int selftok_linear_f16_split(const void* a_blk, const void* packed, const float* bias, float* out, void* out_blk, long ldo,
+                             int M, int N, int K, int flags, int* overflow, hipStream_t stream);
+int selftok_linear_f16_split_residual(const void* a_blk, const void* packed, const float* bias,
+                                      const float* resid, long ldr, const float* gate, long gate_stride_b, long gate_stride_t, int T,
+                                      float* out, long ldo, int M, int N, int K, int* overflow, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

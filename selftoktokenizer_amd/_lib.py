@@ -93,6 +93,8 @@ EXT_SIGNATURES = {
     "selftok_img_metrics": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "selftok_vq_topk_workspace_bytes": (_sz, [_i, _i, _i]),
     "selftok_vq_topk_packed_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "selftok_linear_f16_split": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _vp]),
+    "selftok_linear_f16_split_residual": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _l, _l, _i, _vp, _l, _i, _i, _i, _vp, _vp]),
 }
 
 

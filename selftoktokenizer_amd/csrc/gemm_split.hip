@@ -38,70 +38,20 @@
 // tiles, walked in 8-row-block groups, which keeps the A row panels and W column panels of concurrently running
 // work-groups in one L2.
 #include "common.h"
+#include "gemm_split_shared.h"   // tile shape, weight image, split4, gelu_tanh_f, lds_dma16, ResArgs: shared with gemm_f16.hip
 #include "selftok_hip.h"
 #include <stdlib.h>
 
 namespace selftok {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16v __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-constexpr int BM = 256, BN = 128, BK = 32;
-constexpr float LO_SCALE = 2048.0f, LO_INV = 1.0f / 2048.0f;
-constexpr float F16_MAX = 65504.0f;
-
 constexpr int A_G = BM * 16 + 32;          // bytes between k-groups of the activation image (padded)
 constexpr int A_P = 4 * A_G;               // bytes between the hi and lo planes
 constexpr int A_BYTES = 2 * A_P;           // 33024
-constexpr int W_G = BN * 16;               // weight image: linear (filled by LDS-DMA)
-constexpr int W_P = 4 * W_G;
-constexpr int W_BYTES = 2 * W_P;           // 16384
 constexpr int A_STAGES = 2;                // activation images: tile kt (being multiplied) and tile kt+1 (being written)
 constexpr int W_STAGES = 5;                // weight images: tile kt .. kt+3 (three DMAs in flight) + the one freed last
 constexpr int W_AHEAD = 3;                 // the weight DMA of tile kt+3 is issued in iteration kt
 constexpr int W_BASE = A_STAGES * A_BYTES; // 66048
 constexpr int LDS_BYTES = W_BASE + W_STAGES * W_BYTES;   // 147968 of the CU's 163840
-constexpr int GROUP_M = 4;                 // 32 consecutive tiles (one XCD's resident set) = 4 row blocks x 8 column blocks
-
-// GELU(tanh): 0.5 x (1 + tanh(u)) = x sigmoid(2u) = x / (1 + exp(-2u)), u = sqrt(2/pi) (x + 0.044715 x^3).  The sigmoid form needs one
-// v_exp_f32 + one v_rcp_f32 (1 ulp each) instead of ocml's tanhf (~40 VALU ops: the GELU epilogue was 8 % of the fc1 kernel) and has no
-// cancellation in 1 + tanh(u) for negative x; |error| vs the fp64 GELU stays below the tanhf form's (tests/test_gemm_gpu.py).
-// -inf -> NaN and +inf -> +inf as the reference formula gives.
-__device__ __forceinline__ float gelu_tanh_f(float x)
-{
-    const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-    const float u = k0 * (x + k1 * x * x * x);
-    const float e = __builtin_amdgcn_exp2f(u * (-2.0f * 1.4426950408889634f));
-    return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-// four fp32 -> four (hi, lo) fp16 pairs, written with 2-wide vectors so that the residual and its 2^11 scaling are packed
-// VALU ops (v_pk_add_f32 / v_pk_mul_f32): a wave64 VALU instruction occupies its SIMD for 8 cycles, and with two waves per SIMD
-// the split would otherwise keep the VALU pipe as busy as the matrix pipe.  `mx` (optional) tracks max |x| for the range check.
-template <typename V4>
-__device__ __forceinline__ void split4(const V4& v, f16x4& hi, f16x4& lo)
-{
-    // __builtin_convertvector keeps the pair packed: v_cvt_pk_f16_f32, v_cvt_f32_f16 (+ one SDWA form for the upper half),
-    // v_pk_add_f32, v_pk_mul_f32, v_cvt_pk_f16_f32 = 3 VALU ops per element (element-wise casts compile to 4.5)
-    const f32x2v a = {v.x, v.y}, b = {v.z, v.w};
-    const f16x2 ha = __builtin_convertvector(a, f16x2), hb = __builtin_convertvector(b, f16x2);
-    const f32x2v ra = (a - __builtin_convertvector(ha, f32x2v)) * LO_SCALE;                        // exact residual, then 2^11
-    const f32x2v rb = (b - __builtin_convertvector(hb, f32x2v)) * LO_SCALE;
-    const f16x2 la = __builtin_convertvector(ra, f16x2), lb = __builtin_convertvector(rb, f16x2);
-    hi[0] = ha[0]; hi[1] = ha[1]; hi[2] = hb[0]; hi[3] = hb[1];
-    lo[0] = la[0]; lo[1] = la[1]; lo[2] = lb[0]; lo[3] = lb[1];
-}
-template <typename V4>
-__device__ __forceinline__ void split4(const V4& v, f16x4& hi, f16x4& lo, float& mx)
-{
-    split4(v, hi, lo);
-    mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-}
 
 // W [N,K] fp32 row-major -> packed[(nb*KT + kt)][plane][g][n][8]  (halfs), nb = n/128, kt = k/32, g = (k%32)/8
 __global__ __launch_bounds__(256) void pack_weight_kernel(const float* __restrict__ W, _Float16* __restrict__ packed, int N, int K, int* __restrict__ overflow)
@@ -344,24 +294,10 @@ __global__ __launch_bounds__(512, 2) void linear_f16x2_kernel(const float* __res
 // A fragment read (32 rows x one k-group per half wave) then touches each of the 64 banks once per 16 lanes.
 // Rings: 3 activation stages (32 KiB) + 4 weight stages (16 KiB) = the CU's whole 160 KiB; the DMAs of activation tile kt+2 and
 // weight tile kt+3 are issued at the top of iteration kt into the stages iteration kt-1 released at its barrier.
-constexpr int PA_ROW = 64;                       // bytes per row and plane of a 32-deep k-tile
-constexpr int PA_P = BM * PA_ROW;                // 16384
 constexpr int PA_BYTES = 2 * PA_P;               // 32768
 constexpr int PA_STAGES = 3, PW_STAGES = 4;
 constexpr int PW_BASE = PA_STAGES * PA_BYTES;    // 98304
 constexpr int P_LDS_BYTES = PW_BASE + PW_STAGES * W_BYTES;   // 163840
-
-// one LDS-DMA piece: 64 lanes x 16 B from (uniform base + per-lane 32-bit byte offset) to LDS [lds, lds + 1 KiB) in lane order.
-// Inline asm because hipcc will not select the SGPR-base form for the builtin (it rebuilds a 64-bit VGPR address per piece).
-__device__ __forceinline__ void lds_dma16(const void* base, unsigned voff, unsigned lds)
-{
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds) : "memory", "m0");   // M0 declared as clobbered
-}
-
-// fused residual epilogue (RES): out = resid + gate * (A W^T + bias), gate element (row, col) at gate + (row / T) gsb + (row % T) gst + col
-// (per-sample table: gst = 0; per-token table: gsb = 0; gate NULL: out = resid + y).  The multiply and the add are separate
-// fp32 operations, exactly as residual_ln_mod_kernel performs them on the stored y: same bits, one tensor round trip less.
-struct ResArgs { const float* resid; long ldr; const float* gate; long gsb, gst; int T; };
 
 // SK = 1 (small M: a 256-row tile grid has 12 .. 96 work-groups for this model's Linears at one image): gridDim.y work-groups share an
 // output tile, each over K / gridDim.y consecutive k-tiles, and write their raw partial sums (no bias) to plane blockIdx.y of a

@@ -34,7 +34,8 @@ from .weights import DIT_DEPTH, DIT_HEADS, DIT_HIDDEN, POS_MAX_DIT
 
 class MMDiTGPU(ModuleSurface):
     _sd_prefix = "model."
-    GEMM_MODES = ("fp32", "f16x2", "exact")
+    GEMM_MODES = ("fp32", "f16x2", "exact", "f16")
+    SPLIT_MODES = ("f16x2", "f16")      # the modes that share the packed weight images, the split-activation producers and the f16x2 joint attention
     PRESPLIT = True     # f16x2 mode: producers (LN-modulate, attention, fc1+GELU) hand the next Linear its input already split
     EXACT_FUSED_RESIDUAL_LN = True   # gemm='exact': `x + gate * Linear(.)` inside the LayerNorm pass that follows (ops.ex_res_layernorm_mod) instead of the Linear's epilogue
     SPLITK = True       # f16x2 mode, <= ops.SPLITK_MAX_ROWS rows (one .. four images): several work-groups per output tile (ops.f16x2_ksplit)
@@ -74,13 +75,18 @@ class MMDiTGPU(ModuleSurface):
         attn64_f16x2_kernel -- fp32-equivalent split arithmetic on the f16 matrix cores, measured MORE accurate against fp64 than the
         fp32 kernels they replace (tests/test_gemm_gpu.py, tests/test_kernels_gpu.py).  Weights are split once, here.  If a weight
         is outside the fp16 range the mode stays 'fp32'; activations outside it raise `self.overflow` (checked once per decode
-        call by the pipeline, which then recomputes in 'fp32').  Returns the mode in force."""
+        call by the pipeline, which then recomputes in 'fp32').
+        'f16' (LOSSY, labelled: outside the 1e-3 dB of the other modes): everything of 'f16x2' -- the same packed weight
+        images, the same split-activation producers, the same f16x2 joint attention, the same range refusal and overflow flag -- except that
+        the block Linears above ops.SPLITK_MAX_ROWS rows run ops.linear_f16_split: fp16-rounded operands (the hi planes alone), fp32
+        accumulation, one matrix instruction per product.  Rows <= SPLITK_MAX_ROWS stay on the f16x2 split-K route (the single-pass fp16
+        kernel has no split-K variant).  Returns the mode in force."""
         if mode not in self.GEMM_MODES:
             raise ValueError(f"gemm mode {mode!r}: expected one of {self.GEMM_MODES}")
         if mode == "exact":
             self._build_exact()
         self.ctx_tables = self._tables_exact if mode == "exact" else self._tables_fast
-        if mode == "f16x2" and not self._packed:
+        if mode in self.SPLIT_MODES and not self._packed:
             flag = torch.zeros(1, dtype=torch.int32, device=self.device)
             packed = {}
             for name, w in self.w.items():
@@ -89,7 +95,7 @@ class MMDiTGPU(ModuleSurface):
                         and ops.linear_f16x2_supported(w.shape[0], w.shape[1])):
                     packed[name[:-len(".weight")]] = ops.linear_f16x2_pack(w, flag)
             if int(flag.item()) != 0:
-                print("[selftok] f16x2 GEMM mode refused: a weight is outside the fp16 range; staying on fp32 GEMMs")
+                print(f"[selftok] {mode} GEMM mode refused: a weight is outside the fp16 range; staying on fp32 GEMMs")
                 mode = "fp32"
             else:
                 self._packed = packed
@@ -136,10 +142,14 @@ class MMDiTGPU(ModuleSurface):
             return ops.ex_linear(x, w, b, gelu=gelu)
         if isinstance(x, ops.SplitAct):
             assert name in self._packed, f"split activation handed to Linear {name!r}, which has no f16x2-split weight (set_gemm('f16x2') packs the block Linears)"
+            if self._single_f16(x.rows):
+                return ops.linear_f16_split(x, self._packed[name], b, w.shape[0], gelu=gelu, overflow=self.overflow, out_split=out_split)
             return ops.linear_f16x2_split(x, self._packed[name], b, w.shape[0], gelu=gelu, overflow=self.overflow, out_split=out_split,
                                           ksplit=self._ksplit(x.rows, w))
         assert not out_split
-        if self.gemm == "f16x2" and name in self._packed:
+        if self.gemm in self.SPLIT_MODES and name in self._packed:
+            if self._single_f16(x.numel() // x.shape[-1]):
+                return ops.linear_f16_split(x, self._packed[name], b, w.shape[0], gelu=gelu, overflow=self.overflow)
             return ops.linear_f16x2(x, self._packed[name], b, w.shape[0], gelu=gelu, overflow=self.overflow)
         if gelu:
             return ops.linear_gelu(x, w, b)
@@ -148,9 +158,13 @@ class MMDiTGPU(ModuleSurface):
     def _ksplit(self, rows: int, w) -> int:
         return ops.f16x2_ksplit(rows, w.shape[0], w.shape[1]) if self.SPLITK else 1
 
+    def _single_f16(self, rows: int) -> bool:
+        """'f16' mode: does a packed Linear over `rows` rows run the single-pass fp16 kernel?  Small row counts keep the f16x2 split-K route."""
+        return self.gemm == "f16" and rows > ops.SPLITK_MAX_ROWS
+
     def _pre(self, name) -> bool:
         """does Linear `name` take its input as a split activation?"""
-        return self.PRESPLIT and self.gemm == "f16x2" and name in self._packed
+        return self.PRESPLIT and self.gemm in self.SPLIT_MODES and name in self._packed
 
     def _ln(self, consumer, x, **kw):
         """residual_ln_mod whose normalised output feeds Linear `consumer`: split form if that Linear takes it"""
@@ -182,8 +196,12 @@ class MMDiTGPU(ModuleSurface):
         if isinstance(lin_in, ops.SplitAct):
             assert lin_name in self._packed, f"split activation handed to Linear {lin_name!r}, which has no f16x2-split weight"
             w, b = self.w[lin_name + ".weight"], self.w[lin_name + ".bias"]
-            x = ops.linear_f16x2_split_residual(lin_in, self._packed[lin_name], b, w.shape[0], x, gate=gate, gate_per_sample=gate_per_sample,
-                                                overflow=self.overflow, ksplit=self._ksplit(lin_in.rows, w))
+            if self._single_f16(lin_in.rows):
+                x = ops.linear_f16_split_residual(lin_in, self._packed[lin_name], b, w.shape[0], x, gate=gate, gate_per_sample=gate_per_sample,
+                                                  overflow=self.overflow)
+            else:
+                x = ops.linear_f16x2_split_residual(lin_in, self._packed[lin_name], b, w.shape[0], x, gate=gate, gate_per_sample=gate_per_sample,
+                                                    overflow=self.overflow, ksplit=self._ksplit(lin_in.rows, w))
             _, n = ops.residual_ln_mod(x, split=split, overflow=self.overflow, **ln_kw)
             return x, n
         return ops.residual_ln_mod(x, y=self.lin(lin_name, lin_in), gate=gate, gate_per_sample=gate_per_sample, split=split,
@@ -285,7 +303,7 @@ class MMDiTGPU(ModuleSurface):
                 oc = None if i == last else ops.ex_attention(cq, ck, cv, NH, *see, slots1=self.K, kmask=kmask)
                 return oc, ops.ex_attention(xq, ck, cv, NH, xk, xv, slots1=self.K, kmask=kmask)
             return attend
-        amode = ops.ATTN_F16X2 if self.gemm == "f16x2" else 0   # 'f16x2': the joint attention runs as split products too
+        amode = ops.ATTN_F16X2 if self.gemm in self.SPLIT_MODES else 0   # 'f16x2' / 'f16': the joint attention runs as split products too
 
         def out(rows, consumer, zero=False):        # attention output buffer: split planes if the proj Linear takes them
             if self._pre(consumer) and amode:

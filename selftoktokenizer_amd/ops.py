@@ -444,6 +444,60 @@ def linear_f16x2_split_residual(xs: SplitAct, packed: torch.Tensor, bias, N: int
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# single-pass fp16 Linear on the same split planes (csrc/gemm_f16.hip): the LOSSY "f16" GEMM mode
+# ----------------------------------------------------------------------------------------------
+def _as_split(x, overflow) -> SplitAct:
+    return x if isinstance(x, SplitAct) else split_f16x2(x, overflow)
+
+
+def linear_f16_split(xs, packed: torch.Tensor, bias, N: int, gelu: bool = False, overflow: torch.Tensor = None, out_split: bool = False):
+    """act(fp16(x) @ fp16(W).T + bias) with fp32 accumulation: linear_f16x2_split with both low planes taken as zero -- fp16-rounded
+    operands, one matrix instruction per product instead of three.  LOSSY (11 significand bits per operand), not fp32-equivalent.
+    `xs`: a SplitAct, or an fp32 tensor [..., K] (fed through split_f16x2); `packed`: linear_f16x2_pack(W), the same image the
+    f16x2 mode holds -- only the hi planes of both are read.  Returns fp32 [..., N], or with out_split a SplitAct with both planes.
+    On fp16-representable operands the result equals linear_f16x2_split's.  There is no split-K variant of this kernel: callers
+    keep row counts <= SPLITK_MAX_ROWS on linear_f16x2_split(..., ksplit=f16x2_ksplit(...)) (MMDiTGPU.lin does)."""
+    xs = _as_split(xs, overflow)
+    _need_cuda(xs.data, packed)
+    K = xs.shape[-1]
+    assert packed.numel() * 2 == 4 * N * K, "packed weight does not match (N, K)"
+    M, lead = xs.rows, xs.shape[:-1]
+    lib = _lib.load()
+    flags = LINEAR_GELU if gelu else 0
+    if out_split:
+        out = SplitAct((*lead, N), xs.device)
+        _lib.check(lib.selftok_linear_f16_split(_p(xs.data), _p(packed), _p(bias), None, _p(out.data), N, M, N, K, flags, _p(overflow), _stream()),
+                   "selftok_linear_f16_split")
+        return out
+    out = torch.empty(M, N, dtype=torch.float32, device=xs.device)
+    _lib.check(lib.selftok_linear_f16_split(_p(xs.data), _p(packed), _p(bias), _p(out), None, N, M, N, K, flags, _p(overflow), _stream()),
+               "selftok_linear_f16_split")
+    return out.reshape(*lead, N)
+
+
+def linear_f16_split_residual(xs, packed: torch.Tensor, bias, N: int, resid: torch.Tensor, gate=None,
+                              gate_per_sample: bool = False, overflow: torch.Tensor = None) -> torch.Tensor:
+    """resid + gate * linear_f16_split(xs): the fused residual epilogue of linear_f16x2_split_residual (same operations, same order)
+    on the single-pass fp16 product.  Arguments as there; `xs` may be an fp32 tensor."""
+    xs = _as_split(xs, overflow)
+    _need_cuda(xs.data, packed, resid)
+    K = xs.shape[-1]
+    assert packed.numel() * 2 == 4 * N * K
+    assert resid.dim() == 3 and resid.is_contiguous() and resid.dtype == torch.float32 and resid.shape[-1] == N
+    B, T, _ = resid.shape
+    M = B * T
+    assert xs.rows == M
+    gsb = gst = 0
+    if gate is not None:
+        assert gate.dim() == 2 and gate.stride(1) == 1 and gate.shape == ((B, N) if gate_per_sample else (T, N))
+        gsb, gst = (gate.stride(0), 0) if gate_per_sample else (0, gate.stride(0))
+    out = torch.empty_like(resid)
+    _lib.check(_lib.load().selftok_linear_f16_split_residual(_p(xs.data), _p(packed), _p(bias), _p(resid), N, _p(gate), gsb, gst, T,
+                                                             _p(out), N, M, N, K, _p(overflow), _stream()), "selftok_linear_f16_split_residual")
+    return out
+
+
 def silu(x):
     _need_cuda(x)
     x = x.contiguous()

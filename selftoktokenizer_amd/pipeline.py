@@ -164,8 +164,9 @@ class SelftokPipeline():
                  vae_encode_mode: Optional[str] = None, vae_decode_mode: Optional[str] = None):
         """cfg: parse_args_from_yaml(...) ; ckpt_path: tokenizer .pth ; sd3_path: diffusers SD3 folder (…/vae/…).
         `state_dict` / `vae_state_dict` (extensions) bypass the files, e.g. with weights.synthetic_state_dict().
-        `gemm` (extension): arithmetic of the MMDiT block Linears, 'fp32' (hipBLASLt fp32) or 'f16x2' (fp32-equivalent
-        split GEMM on the f16 matrix cores, csrc/gemm_split.hip); default DEFAULT_GEMM.
+        `gemm` (extension): arithmetic of the MMDiT block Linears, 'fp32' (hipBLASLt fp32), 'f16x2' (fp32-equivalent
+        split GEMM on the f16 matrix cores, csrc/gemm_split.hip), 'exact' (the reference's bits) or 'f16' (LOSSY: fp16-rounded
+        operands, fp32 accumulation, csrc/gemm_f16.hip -- for bulk decoding, outside the north star's 1e-3 dB); default DEFAULT_GEMM.
         `vae_encode_mode` / `vae_decode_mode` (extensions; `vae_mode` sets both): arithmetic of the two halves of the SD3 VAE (vae.AutoencoderKLGPU).
         'exact': every reduction in the summation ORDER of the reference's torch-CPU run (csrc/vae_exact.hip, fp32 matrix cores) -- encoder: latents and
         token ids from pixels equal the reference's bit for bit; decoder: pixels equal the reference's decode of the same latents, incl. its batch
@@ -369,7 +370,7 @@ class SelftokPipeline():
         return gemm_tune.enabled() if (self.tune_gemm and self.gemm_tune_report and self.model.model.gemm == "fp32") else contextlib.nullcontext()
 
     def set_gemm(self, mode: str) -> str:
-        """switch the MMDiT between 'fp32', 'f16x2' and 'exact' (see MMDiTGPU.set_gemm); returns the mode in force.  Unless the decoder's arithmetic was
+        """switch the MMDiT between 'fp32', 'f16x2', 'exact' and the lossy 'f16' (see MMDiTGPU.set_gemm); returns the mode in force.  Unless the decoder's arithmetic was
         chosen explicitly (`vae_decode_mode` / `vae_mode`), 'exact' brings the exact-order VAE decoder with it (the mode whose pixels are the reference's
         bit for bit) and the other modes return to the default decoder."""
         got = self.model.model.set_gemm(mode)
@@ -381,18 +382,19 @@ class SelftokPipeline():
 
     @torch.no_grad()
     def _checked(self, run):
-        """run() -> latent.  In 'f16x2' GEMM mode an activation outside the fp16 range (|a| >= 65504) invalidates the
+        """run() -> latent.  In the 'f16x2' and 'f16' GEMM modes an activation outside the fp16 range (|a| >= 65504) invalidates the
         result (sticky device flag, one host read per call): redo the call on the fp32 library GEMMs."""
         dit = self.model.model
         out = run()
-        if dit.gemm == "f16x2" and int(dit.overflow.item()) != 0:
-            print("[selftok] f16x2 GEMM: activation outside the fp16 range -> recomputing this call with fp32 GEMMs")
+        mode = dit.gemm
+        if mode in dit.SPLIT_MODES and int(dit.overflow.item()) != 0:
+            print(f"[selftok] {mode} GEMM: activation outside the fp16 range -> recomputing this call with fp32 GEMMs")
             dit.overflow.zero_()
             dit.set_gemm("fp32")
             try:
                 out = run()
             finally:
-                dit.set_gemm("f16x2")              # the split weights are kept: no re-pack
+                dit.set_gemm(mode)                 # the split weights are kept: no re-pack
         return out
 
     @torch.no_grad()

@@ -27,7 +27,7 @@ ap.add_argument("--renderer-pretrained", default=None)
 ap.add_argument("--data_size", type=int, default=256)
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--seed", type=int, default=1234)
-ap.add_argument("--gemm", default=None, choices=["fp32", "f16x2", "exact"], help="exact: every operation in the reference's torch-CPU order (bit-equal pixels, the parity mode)")
+ap.add_argument("--gemm", default=None, choices=["fp32", "f16x2", "exact", "f16"], help="exact: every operation in the reference's torch-CPU order (bit-equal pixels, the parity mode); f16: the lossy single-pass fp16 Linears (outside the 1e-3 dB of the other modes)")
 ap.add_argument("--device-io", action="store_true", help="resize / crop / normalise the decoded files on the GPU (preprocess.DeviceLoader): the same values, bit for bit")
 ap.add_argument("--ssim", action="store_true", help="also the SSIM of every image (11 x 11 Gaussian window, sigma 1.5, valid region); both figures then come from one device call per batch")
 ap.add_argument("--metrics-u8", action="store_true", help="with --ssim: take PSNR and SSIM on the uint8 bytes save_image would write instead of the float tensors")
