@@ -121,6 +121,22 @@ int selftok_linear_f16_split_residual(const void* a_blk, const void* packed, con
                                       const float* resid, long ldr, const float* gate, long gate_stride_b, long gate_stride_t, int T,
                                       float* out, long ldo, int M, int N, int K, int* overflow, hipStream_t stream);
 
+/* ---- single-pass fp16 joint attention (the attention of the "f16" mode) ---------------------------------
+ * selftok_attn_f32 / selftok_attn_kmask_f32 with ONE fp16 matrix instruction per product -- LOSSY (11 significand bits per
+ * operand), not fp32-equivalent.  Arithmetic of record, operands fp32 q, k, v, head_dim 64:
+ *     c = scale * 1.4426950408889634f (fp32 product);  q~ = fp16(q * c) (fp32 multiply, then round to nearest even);
+ *     k~ = fp16(k), v~ = fp16(v);  s_j = sum_d q~_d k~_jd (exact fp16 products, fp32 accumulation, log2 domain);
+ *     online softmax in fp32 against the true running maximum;  p~ = fp16(exp2(s - m));  O += v~^T p~;  the row sum adds the
+ *     rounded p~ in fp32;  o = O / l -- a convex combination of fp16(v) rows up to fp32 rounding.
+ * The descriptor is selftok_attn_f32's.  kmask == NULL: desc->kvis rules (may be NULL).  Otherwise the words and limits of
+ * selftok_attn_kmask_f32: kvis must be NULL, seg[0].len <= 2048, kmask_bs >= ceil(seg[0].len / 32).  Visibility, dead rows
+ * (not written) and seg0_sees_seg1 are those entries'; an invisible key contributes an exact zero and its contents (NaN and Inf
+ * included) reach neither the output nor the flag.  desc->mode is not read.  Output per segment: fp32 `o`, or a split activation
+ * desc->o_blk[s] (16-byte aligned) with BOTH planes, the lo plane being the residual of the fp32 output.  |q * c|, |k| or
+ * |v| >= 65504 gives a non-finite output and ORs bit 2 into *desc->overflow.  head_dim != 64 returns SELFTOK_EINVAL with a
+ * message; B == 0 or no query row returns 0 without a launch. */
+int selftok_attn_f16(const selftok_attn_desc* desc, const unsigned* kmask, long kmask_bs, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

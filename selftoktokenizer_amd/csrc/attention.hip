@@ -20,84 +20,14 @@
 // cross-half shuffle), exponentiates in registers, and feeds P^T straight back as the B operand of the
 // O^T += V^T P^T MFMAs -- the accumulator register index IS the k index, no LDS round trip for P.
 // K tiles are staged [key][68] (b128 reads, conflict-free), V tiles [key][64] (b32 reads, conflict-free).
-#include "common.h"
-#include "selftok_hip.h"
+#include "attention_shared.h"
 #include "selftok_hip_ext.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace selftok {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct AttnSeg {
-    const float* q;   // may be NULL: segment contributes keys/values only
-    const float* k;
-    const float* v;
-    float* o;
-    _Float16* o_blk;  // f16x2 kernel: split-activation output (or NULL): the segment's [B * len, H * 64] matrix
-    int len;          // rows in this segment
-    long q_rs, k_rs, v_rs, o_rs;   // row strides (floats)
-    long q_bs, k_bs, v_bs, o_bs;   // batch strides (floats)
-};
-
-struct AttnParams {
-    AttnSeg seg[2];
-    int B, H;
-    const int* kvis;        // [B] or NULL
-    int seg0_sees_seg1;
-    float scale;
-    int qtiles;             // 128-row query tiles per (sample, head), both segments
-    int xcd_remap;
-    int prio;               // attn64_dma_kernel: raise the wave's issue priority inside its MFMA clusters (s_setprio)
-    const unsigned* kmask;  // <true> instantiations: [B, kmask_bs] words, bit j & 31 of word j >> 5 = segment-0 key j is visible
-    long kmask_bs;
-};
-
-constexpr int KT = 32;           // keys per tile
 constexpr int KSTR = 68;         // padded K row stride in LDS (floats)
-constexpr int QROWS = 128;       // query rows per workgroup
-
-// ---------------------------------------------------------------------------------------
-// Per-sample key bit mask (selftok_attn_kmask_f32, include/selftok_hip_ext.h).  The three head_dim-64 kernels below are templates on
-// KMASK; the <false> instantiations are the kernels of selftok_attn_f32 and contain none of this (`if constexpr`).
-//   * lane i of every wave holds word i of the sample (bits >= seg[0].len cleared): one vector load per wave, after which a
-//     tile's word is a v_readlane into an SGPR and the set of tiles with a visible key is one 64-bit ballot.
-//   * tiles whose word is 0 are never staged or multiplied: the walk pops the next set bit of that ballot.
-//   * a tile's word doubles as the ragged-tile mask (bits past the end of the segment are clear), so a full word takes the
-//     unmasked path and anything else the wave-uniform "ragged tile" branch.
-//   * a segment-0 query row whose bit is clear is dead: not stored; a wave whose 32 rows are dead stages and synchronises but
-//     issues no MFMA; a workgroup whose 128 rows are dead returns before any q / k / v load.
-// ---------------------------------------------------------------------------------------
-struct KMaskWalk {
-    unsigned wv;                  // lane i: word i
-    unsigned long long rem;       // segment-0 tiles with a visible key that are not staged yet
-    unsigned roww;                // visibility word of this wave's 32 query rows (all ones for segment-1 rows)
-    int cur, nxt;                 // segment-0 tile being consumed / being staged
-    __device__ __forceinline__ int pop() { const int i = __builtin_ctzll(rem); rem &= rem - 1; return i; }
-    __device__ __forceinline__ unsigned word(int i) const { return (unsigned)__builtin_amdgcn_readlane((int)wv, i); }
-};
-// -> false: every query row of this workgroup is dead
-__device__ __forceinline__ bool kmask_init(KMaskWalk& M, const unsigned* __restrict__ kmask, long kmask_bs, int b, int len0, int s, int r0, int wave, int lane)
-{
-    const int nw = (len0 + 31) >> 5;                          // <= 64, checked by the launcher
-    M.wv = 0;
-    if (lane < nw) {
-        M.wv = kmask[(size_t)b * kmask_bs + lane];
-        if (lane == nw - 1 && (len0 & 31)) M.wv &= (1u << (len0 & 31)) - 1u;
-    }
-    M.rem = __ballot(M.wv != 0);
-    M.roww = ~0u; M.cur = 0; M.nxt = 0;
-    if (s == 0) {
-        const int w0 = r0 >> 5;                               // r0 < len0: w0 < nw
-        if (((M.rem >> w0) & 0xfull) == 0) return false;
-        const int wi = w0 + __builtin_amdgcn_readfirstlane(wave);
-        M.roww = wi < nw ? M.word(wi) : 0u;
-    }
-    return true;
-}
-// visibility word of a tile without a mask: all ones, or the low bits of a ragged last tile
-__device__ __forceinline__ unsigned ragged_word(int key0, int nkeys) { return key0 + KT > nkeys ? (1u << (nkeys - key0)) - 1u : ~0u; }
 
 template <bool KMASK>
 __global__ __launch_bounds__(256) void attn64_kernel(AttnParams P)
@@ -108,18 +38,8 @@ __global__ __launch_bounds__(256) void attn64_kernel(AttnParams P)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, col = lane & 31;
-    // XCD-aware work mapping: workgroup `orig` runs on XCD orig % 8 (observed dispatch order; speed only, never
-    // correctness).  Give every XCD a contiguous range of work items so that the q-tiles of one (sample, head), which
-    // re-read the same K/V, share one L2 instead of pulling K/V through the fabric once per XCD.
     int qt, h, b;
-    {
-        const int T = gridDim.x, orig = blockIdx.x;
-        const int q8 = T >> 3, r8 = T & 7, xcd = orig & 7, idx = orig >> 3;
-        const int w = P.xcd_remap ? (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx : orig;
-        qt = w % P.qtiles;
-        h = (w / P.qtiles) % P.H;
-        b = w / (P.qtiles * P.H);
-    }
+    attn_work_item(P, P.xcd_remap != 0, qt, h, b);
 
     int n0 = P.seg[0].len;
     if (P.kvis) { int kv = P.kvis[b] + 1; n0 = kv < n0 ? (kv < 0 ? 0 : kv) : n0; }
@@ -363,14 +283,7 @@ __global__ __launch_bounds__(256) void attn64_dma_kernel(AttnParams P)
     const int half = lane >> 5, col = lane & 31;
     const bool prio = P.prio != 0;
     int qt, h, b;
-    {
-        const int T = gridDim.x, orig = blockIdx.x;
-        const int q8 = T >> 3, r8 = T & 7, xcd = orig & 7, idx = orig >> 3;
-        const int w = P.xcd_remap ? (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx : orig;
-        qt = w % P.qtiles;
-        h = (w / P.qtiles) % P.H;
-        b = w / (P.qtiles * P.H);
-    }
+    attn_work_item(P, P.xcd_remap != 0, qt, h, b);
     int n0 = P.seg[0].len;
     if (P.kvis) { int kv = P.kvis[b] + 1; n0 = kv < n0 ? (kv < 0 ? 0 : kv) : n0; }
     const int rows0 = P.seg[0].q ? n0 : 0;
@@ -587,37 +500,11 @@ __global__ __launch_bounds__(256) void attn64_dma_kernel(AttnParams P)
 // key (r&3) + 8 (r>>2) + 4 half), so P^T goes from the softmax registers straight into the B operand; d' = (d&3)*16 + d/4
 // makes the transposing ds_write_b64 of the staging pass bank-conflict free and still lets the epilogue store float4s.
 // ---------------------------------------------------------------------------------------
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int KG_STRIDE = 32 * 16 + 16;          // bytes between d-groups of the K image (padded: conflict-free b128 staging writes)
 constexpr int K_PLANE = 8 * KG_STRIDE;           // 4224
 constexpr int V_PLANE = 4 * 64 * 16;             // 4096
 constexpr int KV_BUF = 2 * K_PLANE + 2 * V_PLANE;   // 16640 bytes per staged tile
 
-// (a, b) -> packed fp16 pair hi = rne(a, b) and the packed residual lo = rne(a - hi.x, b - hi.y).  Plain C++ on purpose: an
-// inline-asm version around v_fma_mix_f32 (4 ops per pair instead of 6) measured 12 % SLOWER -- every asm statement costs
-// boundary s_nops and v_movs to gather its scalar outputs into the 128-bit MFMA operands.
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-struct HiLo { unsigned hi, lo; };
-__device__ __forceinline__ HiLo split_pair(float a, float b)
-{
-    const f32x2 x = {a, b};
-    const h16x2 h = __builtin_convertvector(x, h16x2);                                             // v_cvt_pk_f16_f32
-    const h16x2 l = __builtin_convertvector(x - __builtin_convertvector(h, f32x2), h16x2);         // 2 cvt + v_pk_add + v_cvt_pk
-    return HiLo{__builtin_bit_cast(unsigned, h), __builtin_bit_cast(unsigned, l)};
-}
-// the Linear kernels' form of the split (gemm_split.hip `split4`): the residual is carried scaled by 2^11
-__device__ __forceinline__ HiLo split_pair_scaled(float a, float b)
-{
-    const f32x2 x = {a, b};
-    const h16x2 h = __builtin_convertvector(x, h16x2);
-    const h16x2 l = __builtin_convertvector((x - __builtin_convertvector(h, f32x2)) * 2048.0f, h16x2);
-    return HiLo{__builtin_bit_cast(unsigned, h), __builtin_bit_cast(unsigned, l)};
-}
-__device__ __forceinline__ h16x8 as_h8(const u32x4& v) { return __builtin_bit_cast(h16x8, v); }
 // tools/ builds only: what the staging pass would cost if K / V arrived already split (one conversion per pair stands in for the
 // v_perm of a 16-bit transpose; results are hi-only, i.e. wrong in the low bits -- a timing probe, tools/bench_attn.py)
 #if defined(SELFTOK_TUNE) && defined(SELFTOK_ATTN_PRESPLIT_PROBE)
@@ -638,14 +525,7 @@ __global__ __launch_bounds__(256, 2) void attn64_f16x2_kernel(AttnParams P, int*
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, col = lane & 31;
     int qt, h, b;
-    {
-        const int T = gridDim.x, orig = blockIdx.x;
-        const int q8 = T >> 3, r8 = T & 7, xcd = orig & 7, idx = orig >> 3;
-        const int w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        qt = w % P.qtiles;
-        h = (w / P.qtiles) % P.H;
-        b = w / (P.qtiles * P.H);
-    }
+    attn_work_item(P, true, qt, h, b);
     int n0 = P.seg[0].len;
     if (P.kvis) { int kv = P.kvis[b] + 1; n0 = kv < n0 ? (kv < 0 ? 0 : kv) : n0; }
     const int rows0 = P.seg[0].q ? n0 : 0;
@@ -962,31 +842,13 @@ using namespace selftok;
 static int attn_launch(const selftok_attn_desc* d, const unsigned* kmask, long kmask_bs, hipStream_t stream)
 {
     if (!d || d->B < 0 || d->H <= 0) { set_last_error("attn: bad descriptor"); return SELFTOK_EINVAL; }
-    if (kmask) {
-        if (d->kvis) { set_last_error("attn(kmask): kvis and kmask are exclusive"); return SELFTOK_EINVAL; }
-        if (d->head_dim != 64) { set_last_error("attn(kmask): head_dim 64 only"); return SELFTOK_EINVAL; }
-        if (d->seg[0].len > 64 * KT) { set_last_error("attn(kmask): segment 0 has more than 2048 keys (64 mask words)"); return SELFTOK_EINVAL; }
-        if (((size_t)kmask & 3) != 0 || kmask_bs < (d->seg[0].len + KT - 1) / KT) { set_last_error("attn(kmask): kmask_bs < ceil(seg[0].len / 32) or unaligned mask"); return SELFTOK_EINVAL; }
-    }
+    if (kmask) { const int rc = attn_kmask_check(d, kmask, kmask_bs); if (rc != SELFTOK_OK) return rc; }
     if (d->B == 0) return SELFTOK_OK;
     if (d->head_dim == 64) {
         AttnParams P;
-        for (int s = 0; s < 2; ++s) {
-            const selftok_attn_seg& a = d->seg[s];
-            const bool osplit = d->mode == SELFTOK_ATTN_F16X2 && d->o_blk[s] != nullptr;
-            if (d->o_blk[s] && (d->mode != SELFTOK_ATTN_F16X2 || ((size_t)d->o_blk[s] & 15))) { set_last_error("attn: split outputs need the f16x2 mode and 16-byte alignment"); return SELFTOK_EINVAL; }
-            if (a.len < 0 || (a.len > 0 && (!a.k || !a.v)) || (a.q && !a.o && !osplit)) { set_last_error("attn: bad segment"); return SELFTOK_EINVAL; }
-            if (((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.q_bs | a.k_bs | a.v_bs | a.o_bs) & 3) != 0) { set_last_error("attn: strides must be multiples of 4 floats"); return SELFTOK_EINVAL; }
-            P.seg[s] = AttnSeg{a.len > 0 ? a.q : nullptr, a.k, a.v, a.o, (_Float16*)d->o_blk[s], a.len, a.q_rs, a.k_rs, a.v_rs, a.o_rs, a.q_bs, a.k_bs, a.v_bs, a.o_bs};
-        }
-        P.B = d->B; P.H = d->H; P.kvis = d->kvis; P.seg0_sees_seg1 = d->seg0_sees_seg1; P.scale = d->scale;
-        int t0 = P.seg[0].q ? (P.seg[0].len + QROWS - 1) / QROWS : 0;
-        int t1 = P.seg[1].q ? (P.seg[1].len + QROWS - 1) / QROWS : 0;
-        if (t0 + t1 == 0) return SELFTOK_OK;
-        P.qtiles = t0 + t1;
-        P.xcd_remap = 1;
-        P.prio = 0;
-        P.kmask = kmask; P.kmask_bs = kmask_bs;
+        { const int rc = attn_params64(d, d->mode == SELFTOK_ATTN_F16X2, kmask, kmask_bs, P); if (rc != SELFTOK_OK) return rc; }
+        if (P.qtiles == 0) return SELFTOK_OK;
+        const int t0 = P.seg[0].q ? (P.seg[0].len + QROWS - 1) / QROWS : 0, t1 = P.qtiles - t0;
 #ifdef SELFTOK_TUNE
         { const char* e = getenv("SELFTOK_ATTN_PRIO"); if (e) P.prio = atoi(e); }
 #endif

@@ -39,10 +39,12 @@ class MMDiTGPU(ModuleSurface):
     PRESPLIT = True     # f16x2 mode: producers (LN-modulate, attention, fc1+GELU) hand the next Linear its input already split
     EXACT_FUSED_RESIDUAL_LN = True   # gemm='exact': `x + gate * Linear(.)` inside the LayerNorm pass that follows (ops.ex_res_layernorm_mod) instead of the Linear's epilogue
     SPLITK = True       # f16x2 mode, <= ops.SPLITK_MAX_ROWS rows (one .. four images): several work-groups per output tile (ops.f16x2_ksplit)
+    ATTENTION_MODES = ("split", "f16")   # arithmetic of the joint attention in the split GEMM modes; 'f16' (LOSSY) only with gemm='f16'
 
     def __init__(self, sd: Dict[str, torch.Tensor], device, K: int, renderer: bool = False, gemm: str = "fp32"):
         self.device, self.K, self.renderer = device, K, renderer
         self.gemm = "fp32"
+        self.attention = "split"                                            # 'f16': the joint attention on ops.ATTN_F16 (set_gemm('f16', attention='f16'))
         self._packed = {}                                                   # linear name -> f16x2-split weight image
         self._mod_cache = {}                                                # (timestep name, gemm mode) -> modulations of a single-image step
         self._capture_refs = None                                           # list while a caller captures a hipGraph (see _step_modulations)
@@ -69,7 +71,7 @@ class MMDiTGPU(ModuleSurface):
             self.set_gemm(gemm)
 
     # ---- GEMM arithmetic of the block Linears ---------------------------------------------------
-    def set_gemm(self, mode: str) -> str:
+    def set_gemm(self, mode: str, attention: Optional[str] = None) -> str:
         """'fp32': hipBLASLt fp32 GEMMs (PyTorch-ROCm) + the fp32-input-MFMA attention kernel.  'f16x2': the qkv / proj / fc1 / fc2
         Linears of the 24 joint blocks (99.6 % of the decode FLOPs) run on ops.linear_f16x2 and the joint attention on
         attn64_f16x2_kernel -- fp32-equivalent split arithmetic on the f16 matrix cores, measured MORE accurate against fp64 than the
@@ -80,9 +82,17 @@ class MMDiTGPU(ModuleSurface):
         images, the same split-activation producers, the same f16x2 joint attention, the same range refusal and overflow flag -- except that
         the block Linears above ops.SPLITK_MAX_ROWS rows run ops.linear_f16_split: fp16-rounded operands (the hi planes alone), fp32
         accumulation, one matrix instruction per product.  Rows <= SPLITK_MAX_ROWS stay on the f16x2 split-K route (the single-pass fp16
-        kernel has no split-K variant).  Returns the mode in force."""
+        kernel has no split-K variant).
+        `attention` (opt-in, LOSSY): None or 'split' is the attention described above; 'f16' -- legal only together with
+        mode 'f16', ValueError otherwise -- runs every joint-attention call, at every row count, on the single-pass fp16 kernel
+        (ops.ATTN_F16, csrc/attention_f16.hip).  A call without the argument resets it.  Returns the mode in force."""
         if mode not in self.GEMM_MODES:
             raise ValueError(f"gemm mode {mode!r}: expected one of {self.GEMM_MODES}")
+        attention = "split" if attention is None else attention
+        if attention not in self.ATTENTION_MODES:
+            raise ValueError(f"attention {attention!r}: expected None or one of {self.ATTENTION_MODES}")
+        if attention == "f16" and mode != "f16":
+            raise ValueError(f"attention='f16' is the attention of the lossy gemm mode 'f16', not of {mode!r}")
         if mode == "exact":
             self._build_exact()
         self.ctx_tables = self._tables_exact if mode == "exact" else self._tables_fast
@@ -100,6 +110,7 @@ class MMDiTGPU(ModuleSurface):
             else:
                 self._packed = packed
         self.gemm = mode
+        self.attention = attention if mode == "f16" else "split"          # a refused 'f16' (weights out of range) falls back with the mode
         return mode
 
     # ---- 'exact': every Linear / LayerNorm / GELU / SiLU / attention as the sequence of fp32 operations torch-CPU executes for the reference ----
@@ -304,6 +315,8 @@ class MMDiTGPU(ModuleSurface):
                 return oc, ops.ex_attention(xq, ck, cv, NH, xk, xv, slots1=self.K, kmask=kmask)
             return attend
         amode = ops.ATTN_F16X2 if self.gemm in self.SPLIT_MODES else 0   # 'f16x2' / 'f16': the joint attention runs as split products too
+        if self.gemm == "f16" and self.attention == "f16":
+            amode = ops.ATTN_F16                                          # opt-in: one fp16 matrix instruction per product, every row count
 
         def out(rows, consumer, zero=False):        # attention output buffer: split planes if the proj Linear takes them
             if self._pre(consumer) and amode:

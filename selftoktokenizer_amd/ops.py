@@ -597,6 +597,7 @@ def _seg(q, k, v, o):
 
 
 ATTN_F16X2 = 1
+ATTN_F16 = 2        # LOSSY single-pass fp16 products (selftok_attn_f16, csrc/attention_f16.hip): the attention of the 'f16' GEMM mode
 
 
 def pack_key_mask(mask: torch.Tensor) -> torch.Tensor:
@@ -614,7 +615,9 @@ def attention(seg0, seg1, heads, head_dim, kvis=None, seg0_sees_seg1=True, scale
               kmask=None, kmask_bs=None):
     """seg = (q, k, v, o) tuples of [B,L,heads*head_dim] views (q and o None: keys/values only; seg None: empty).
     Writes into the `o` views.  kvis: int32 [B] or None.  mode = ATTN_F16X2: f16x2-split matrix products (head_dim 64),
-    `overflow` (int32 [1] device tensor) gets bit 2 if an operand is outside the fp16 range.
+    `overflow` (int32 [1] device tensor) gets bit 2 if an operand is outside the fp16 range.  mode = ATTN_F16 (head_dim 64 only, LOSSY):
+    one fp16 matrix instruction per product on fp16-rounded q * c, k, v and probabilities (include/selftok_hip_ext.h: selftok_attn_f16); the same flag,
+    the same outputs (fp32 views or SplitActs), with or without kmask.
     kmask: int32 / uint32 [B, W] words of a per-sample visibility pattern over the segment-0 keys (`pack_key_mask`; exclusive with
     kvis; bits past the segment's length are ignored), kmask_bs: words per sample (default: kmask's row stride)."""
     lib = _lib.load()
@@ -623,7 +626,7 @@ def attention(seg0, seg1, heads, head_dim, kvis=None, seg0_sees_seg1=True, scale
     _need_cuda(ref[1])
     d.seg[0] = _seg(*seg0) if seg0 is not None else _lib.AttnSeg()
     d.seg[1] = _seg(*seg1) if seg1 is not None else _lib.AttnSeg()
-    for i, sg in enumerate((seg0, seg1)):               # `o` given as a SplitAct [B,L,H*Dh]; f16x2 mode only
+    for i, sg in enumerate((seg0, seg1)):               # `o` given as a SplitAct [B,L,H*Dh]; f16x2 and f16 modes only
         if sg is not None and isinstance(sg[3], SplitAct):
             d.o_blk[i] = sg[3].data.data_ptr()
     d.B, d.H, d.head_dim = ref[1].shape[0], heads, head_dim
@@ -632,13 +635,19 @@ def attention(seg0, seg1, heads, head_dim, kvis=None, seg0_sees_seg1=True, scale
         d.kvis = kvis.data_ptr()
     d.seg0_sees_seg1 = 1 if seg0_sees_seg1 else 0
     d.scale = float(scale if scale is not None else head_dim ** -0.5)
-    d.mode = int(mode) if head_dim == 64 else 0
+    f16 = int(mode) == ATTN_F16
+    d.mode = int(mode) if (head_dim == 64 and not f16) else 0
     d.overflow = _p(overflow)
     import ctypes
+    bs = 0
     if kmask is not None:
         assert kmask.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and kmask.is_cuda and kmask.dim() == 2
         assert kmask.shape[0] == d.B and kmask.stride(1) == 1
         bs = int(kmask.stride(0) if kmask_bs is None else kmask_bs)
+    if f16:                     # one entry with and without a mask; it refuses head_dim != 64 itself
+        _lib.check(lib.selftok_attn_f16(ctypes.byref(d), _p(kmask), bs, _stream()), "selftok_attn_f16")
+        return
+    if kmask is not None:
         _lib.check(lib.selftok_attn_kmask_f32(ctypes.byref(d), kmask.data_ptr(), bs, _stream()), "selftok_attn_kmask_f32")
         return
     _lib.check(lib.selftok_attn_f32(ctypes.byref(d), _stream()), "selftok_attn_f32")
