@@ -23,6 +23,9 @@
 // cost as much as the matrix work.  Per iteration and wave: 16 fragment reads, 6 DMA pieces (4 activation + 2 weight), as before.
 // K / 32 odd: the last stage's second half is staged from the last tile again (inside the tensor) and is not multiplied.
 //
+// The work-group -> tile map and the argument contract of the entry points are the f16x2 kernels' own: one definition each, in
+// gemm_split_shared.h.
+//
 // Small row counts: there is no split-K variant of this kernel.  The caller keeps rows <= SPLITK_MAX_ROWS on the f16x2 split-K route
 // (ops.py, mmdit.py).
 #include "common.h"
@@ -51,19 +54,8 @@ __global__ __launch_bounds__(512, 2) void linear_f16_pre_kernel(const _Float16* 
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    // ---- tile id: XCD-contiguous renumbering (bijective), then grouped-M walk (as the f16x2 kernels) ----
     int mb, nb;
-    {
-        const int T = gridDim.x, orig = blockIdx.x;
-        const int q8 = T >> 3, r8 = T & 7, xcd = orig & 7, idx = orig >> 3;
-        const int w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        const int per_group = GROUP_M * nblocks;
-        const int group = w / per_group, first_m = group * GROUP_M;
-        const int gsz = (mblocks - first_m) < GROUP_M ? (mblocks - first_m) : GROUP_M;
-        const int in = w - group * per_group;
-        mb = first_m + in % gsz;
-        nb = in / gsz;
-    }
+    tile_of_workgroup(mblocks, nblocks, mb, nb);                    // gemm_split_shared.h
     const int m0 = mb * BM, n0 = nb * BN;
     const int KT = K / BK, KL = KT - 1;                             // 32-deep k-tiles of the operands
     const int NI = (KT + 1) >> 1, IL = NI - 1;                      // 64-deep iterations
@@ -251,14 +243,9 @@ extern "C" {
 int selftok_linear_f16_split(const void* a_blk, const void* packed, const float* bias, float* out, void* out_blk, long ldo,
                              int M, int N, int K, int flags, int* overflow, hipStream_t stream)
 {
-    if (M < 0 || N <= 0 || K <= 0 || N % BN || K % BK) { set_last_error("linear_f16_split: need N % 128 == 0 and K % 32 == 0"); return SELFTOK_EINVAL; }
-    if (M == 0) return SELFTOK_OK;
+    const int rc = check_split_linear("linear_f16_split", a_blk, packed, bias, out, out_blk, ldo, M, N, K);
+    if (rc != SELFTOK_OK || M == 0) return rc;
     const bool osplit = out_blk != nullptr;
-    if (!a_blk || !packed || ((size_t)a_blk & 15) || ((size_t)out & 15) || ((size_t)out_blk & 15) || (bias && ((size_t)bias & 15))
-        || (osplit ? out != nullptr : (!out || ldo < N || (ldo & 3)))) {
-        set_last_error("linear_f16_split: bad pointers/strides (a_blk, out, out_blk and bias 16-byte aligned; either out with ldo % 4 == 0, ldo >= N, or out_blk)");
-        return SELFTOK_EINVAL;
-    }
     const int mblocks = (M + BM - 1) / BM, nblocks = N / BN;
     const dim3 grid((unsigned)(mblocks * nblocks));
     const _Float16* ab = (const _Float16*)a_blk;
@@ -274,14 +261,8 @@ int selftok_linear_f16_split_residual(const void* a_blk, const void* packed, con
                                       const float* resid, long ldr, const float* gate, long gate_stride_b, long gate_stride_t, int T,
                                       float* out, long ldo, int M, int N, int K, int* overflow, hipStream_t stream)
 {
-    if (M < 0 || N <= 0 || K <= 0 || N % BN || K % BK) { set_last_error("linear_f16_split_residual: need N % 128 == 0 and K % 32 == 0"); return SELFTOK_EINVAL; }
-    if (M == 0) return SELFTOK_OK;
-    if (!a_blk || !packed || !resid || !out || ldo < N || (ldo & 3) || ldr < N || (ldr & 3) || T <= 0
-        || ((size_t)a_blk & 15) || ((size_t)out & 15) || ((size_t)resid & 15) || (bias && ((size_t)bias & 15))
-        || (gate && (((size_t)gate & 15) || (gate_stride_b & 3) || (gate_stride_t & 3)))) {
-        set_last_error("linear_f16_split_residual: bad pointers/strides (16-byte aligned, strides multiples of 4, T > 0)");
-        return SELFTOK_EINVAL;
-    }
+    const int rc = check_split_linear_residual("linear_f16_split_residual", a_blk, packed, bias, resid, ldr, gate, gate_stride_b, gate_stride_t, T, out, ldo, M, N, K);
+    if (rc != SELFTOK_OK || M == 0) return rc;
     const int mblocks = (M + BM - 1) / BM, nblocks = N / BN;
     hipLaunchKernelGGL((linear_f16_pre_kernel<0, 0, 1>), dim3((unsigned)(mblocks * nblocks)), dim3(512), 0, stream,
                        (const _Float16*)a_blk, (const _Float16*)packed, bias, out, (_Float16*)nullptr, ldo,

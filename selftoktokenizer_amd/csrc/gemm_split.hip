@@ -38,7 +38,7 @@
 // tiles, walked in 8-row-block groups, which keeps the A row panels and W column panels of concurrently running
 // work-groups in one L2.
 #include "common.h"
-#include "gemm_split_shared.h"   // tile shape, weight image, split4, gelu_tanh_f, lds_dma16, ResArgs: shared with gemm_f16.hip
+#include "gemm_split_shared.h"   // tile shape and map, weight image, split4, gelu_tanh_f, lds_dma16, ResArgs, the entries' argument contract: shared with gemm_f16.hip
 #include "selftok_hip.h"
 #include <stdlib.h>
 
@@ -96,19 +96,8 @@ __global__ __launch_bounds__(512, 2) void linear_f16x2_kernel(const float* __res
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    // ---- tile id: XCD-contiguous renumbering (bijective), then grouped-M walk ----
     int mb, nb;
-    {
-        const int T = gridDim.x, orig = blockIdx.x;
-        const int q8 = T >> 3, r8 = T & 7, xcd = orig & 7, idx = orig >> 3;
-        const int w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        const int per_group = GROUP_M * nblocks;
-        const int group = w / per_group, first_m = group * GROUP_M;
-        const int gsz = (mblocks - first_m) < GROUP_M ? (mblocks - first_m) : GROUP_M;
-        const int in = w - group * per_group;
-        mb = first_m + in % gsz;
-        nb = in / gsz;
-    }
+    tile_of_workgroup(mblocks, nblocks, mb, nb);                    // gemm_split_shared.h
     const int m0 = mb * BM, n0 = nb * BN;
     const int KT = K / BK, KL = KT - 1;
 
@@ -318,17 +307,7 @@ __global__ __launch_bounds__(512, 2) void linear_f16x2_pre_kernel(const _Float16
     const int l31 = lane & 31, lh = lane >> 5;
 
     int mb, nb;
-    {
-        const int T = gridDim.x, orig = blockIdx.x;
-        const int q8 = T >> 3, r8 = T & 7, xcd = orig & 7, idx = orig >> 3;
-        const int w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        const int per_group = GROUP_M * nblocks;
-        const int group = w / per_group, first_m = group * GROUP_M;
-        const int gsz = (mblocks - first_m) < GROUP_M ? (mblocks - first_m) : GROUP_M;
-        const int in = w - group * per_group;
-        mb = first_m + in % gsz;
-        nb = in / gsz;
-    }
+    tile_of_workgroup(mblocks, nblocks, mb, nb);                    // gemm_split_shared.h
     const int m0 = mb * BM, n0 = nb * BN;
     const int KTA = K / BK;                                         // k-tiles of the operands (their strides)
     const int KT = SK ? KTA / (int)gridDim.y : KTA, KL = KT - 1;    // k-tiles of this work-group
@@ -752,14 +731,9 @@ int selftok_split_f16x2_f32(const float* x, long ld, void* blk, long rows, int c
 int selftok_linear_f16x2_split(const void* a_blk, const void* packed, const float* bias, float* out, void* out_blk, long ldo,
                                int M, int N, int K, int flags, int* overflow, hipStream_t stream)
 {
-    if (M < 0 || N <= 0 || K <= 0 || N % BN || K % BK) { set_last_error("linear_f16x2_split: need N % 128 == 0 and K % 32 == 0"); return SELFTOK_EINVAL; }
-    if (M == 0) return SELFTOK_OK;
+    const int rc = check_split_linear("linear_f16x2_split", a_blk, packed, bias, out, out_blk, ldo, M, N, K);
+    if (rc != SELFTOK_OK || M == 0) return rc;
     const bool osplit = out_blk != nullptr;
-    if (!a_blk || !packed || ((size_t)a_blk & 15) || ((size_t)out & 15) || ((size_t)out_blk & 15) || (bias && ((size_t)bias & 15))
-        || (osplit ? out != nullptr : (!out || ldo < N || (ldo & 3)))) {
-        set_last_error("linear_f16x2_split: bad pointers/strides (a_blk, out, out_blk and bias 16-byte aligned; either out with ldo % 4 == 0, ldo >= N, or out_blk)");
-        return SELFTOK_EINVAL;
-    }
     const int mblocks = (M + BM - 1) / BM, nblocks = N / BN;
     const dim3 grid((unsigned)(mblocks * nblocks));
     const _Float16* ab = (const _Float16*)a_blk;
@@ -784,14 +758,8 @@ int selftok_linear_f16x2_split_residual(const void* a_blk, const void* packed, c
                                         const float* resid, long ldr, const float* gate, long gate_stride_b, long gate_stride_t, int T,
                                         float* out, long ldo, int M, int N, int K, int* overflow, hipStream_t stream)
 {
-    if (M < 0 || N <= 0 || K <= 0 || N % BN || K % BK) { set_last_error("linear_f16x2_split_residual: need N % 128 == 0 and K % 32 == 0"); return SELFTOK_EINVAL; }
-    if (M == 0) return SELFTOK_OK;
-    if (!a_blk || !packed || !resid || !out || ldo < N || (ldo & 3) || ldr < N || (ldr & 3) || T <= 0
-        || ((size_t)a_blk & 15) || ((size_t)out & 15) || ((size_t)resid & 15) || (bias && ((size_t)bias & 15))
-        || (gate && (((size_t)gate & 15) || (gate_stride_b & 3) || (gate_stride_t & 3)))) {
-        set_last_error("linear_f16x2_split_residual: bad pointers/strides (16-byte aligned, strides multiples of 4, T > 0)");
-        return SELFTOK_EINVAL;
-    }
+    const int rc = check_split_linear_residual("linear_f16x2_split_residual", a_blk, packed, bias, resid, ldr, gate, gate_stride_b, gate_stride_t, T, out, ldo, M, N, K);
+    if (rc != SELFTOK_OK || M == 0) return rc;
     const int mblocks = (M + BM - 1) / BM, nblocks = N / BN;
     hipLaunchKernelGGL((linear_f16x2_pre_kernel<0, 0, 1, 0, 1>), dim3((unsigned)(mblocks * nblocks)), dim3(512), 0, stream,
                        (const _Float16*)a_blk, (const _Float16*)packed, bias, out, (_Float16*)nullptr, ldo,
@@ -805,23 +773,14 @@ size_t selftok_linear_f16x2_splitk_workspace_bytes(int M, int N, int ksplit)
     return (size_t)ksplit * M * N * sizeof(float);
 }
 
-static bool splitk_ok(int K, int ksplit, const void* workspace)
-{
-    return ksplit >= 2 && ksplit <= 64 && (K / BK) % ksplit == 0 && workspace && !((size_t)workspace & 15);
-}
-
 int selftok_linear_f16x2_split_k(const void* a_blk, const void* packed, const float* bias, float* out, void* out_blk, long ldo,
                                  int M, int N, int K, int flags, int ksplit, void* workspace, int* overflow, hipStream_t stream)
 {
     if (ksplit == 1) return selftok_linear_f16x2_split(a_blk, packed, bias, out, out_blk, ldo, M, N, K, flags, overflow, stream);
-    if (M < 0 || N <= 0 || K <= 0 || N % BN || K % BK) { set_last_error("linear_f16x2_split_k: need N % 128 == 0 and K % 32 == 0"); return SELFTOK_EINVAL; }
-    if (M == 0) return SELFTOK_OK;
+    int rc = check_split_linear("linear_f16x2_split_k", a_blk, packed, bias, out, out_blk, ldo, M, N, K);
+    if (rc != SELFTOK_OK || M == 0) return rc;
+    if ((rc = check_splitk("linear_f16x2_split_k", K, ksplit, workspace))) return rc;
     const bool osplit = out_blk != nullptr;
-    if (!a_blk || !packed || ((size_t)a_blk & 15) || ((size_t)out & 15) || ((size_t)out_blk & 15) || (bias && ((size_t)bias & 15))
-        || (osplit ? out != nullptr : (!out || ldo < N || (ldo & 3))) || !splitk_ok(K, ksplit, workspace)) {
-        set_last_error("linear_f16x2_split_k: bad pointers/strides (as linear_f16x2_split), or ksplit not in 2..64 / not a divisor of K / 32, or no 16-byte aligned workspace");
-        return SELFTOK_EINVAL;
-    }
     float* ws = (float*)workspace;
     if (int rc = launch_splitk_partials(a_blk, packed, ws, M, N, K, ksplit, overflow, stream)) return rc;
     const long n = (long)M * (N / 8);
@@ -840,14 +799,9 @@ int selftok_linear_f16x2_split_residual_k(const void* a_blk, const void* packed,
 {
     if (ksplit == 1)
         return selftok_linear_f16x2_split_residual(a_blk, packed, bias, resid, ldr, gate, gate_stride_b, gate_stride_t, T, out, ldo, M, N, K, overflow, stream);
-    if (M < 0 || N <= 0 || K <= 0 || N % BN || K % BK) { set_last_error("linear_f16x2_split_residual_k: need N % 128 == 0 and K % 32 == 0"); return SELFTOK_EINVAL; }
-    if (M == 0) return SELFTOK_OK;
-    if (!a_blk || !packed || !resid || !out || ldo < N || (ldo & 3) || ldr < N || (ldr & 3) || T <= 0
-        || ((size_t)a_blk & 15) || ((size_t)out & 15) || ((size_t)resid & 15) || (bias && ((size_t)bias & 15))
-        || (gate && (((size_t)gate & 15) || (gate_stride_b & 3) || (gate_stride_t & 3))) || !splitk_ok(K, ksplit, workspace)) {
-        set_last_error("linear_f16x2_split_residual_k: bad pointers/strides (as linear_f16x2_split_residual), or ksplit not in 2..64 / not a divisor of K / 32, or no 16-byte aligned workspace");
-        return SELFTOK_EINVAL;
-    }
+    int rc = check_split_linear_residual("linear_f16x2_split_residual_k", a_blk, packed, bias, resid, ldr, gate, gate_stride_b, gate_stride_t, T, out, ldo, M, N, K);
+    if (rc != SELFTOK_OK || M == 0) return rc;
+    if ((rc = check_splitk("linear_f16x2_split_residual_k", K, ksplit, workspace))) return rc;
     float* ws = (float*)workspace;
     if (int rc = launch_splitk_partials(a_blk, packed, ws, M, N, K, ksplit, overflow, stream)) return rc;
     const long n = (long)M * (N / 8);

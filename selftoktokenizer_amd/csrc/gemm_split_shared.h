@@ -1,8 +1,10 @@
 // What the Linear kernels on the split planes share (gemm_split.hip: the f16x2 kernels; gemm_f16.hip: the single-pass fp16 kernel
-// on the same operands): tile shape, the packed weight image, the fp32 -> (hi, lo) split, the GELU, the LDS-DMA piece and the
-// arguments of the fused residual epilogue.  One definition each, so that "the same operations in the same order" is the same code.
+// on the same operands): tile shape, the packed weight image, the work-group -> tile map, the fp32 -> (hi, lo) split, the GELU, the
+// LDS-DMA piece, the arguments of the fused residual epilogue and, for the host, the argument contract of the split-input entry points.
+// One definition each, so that "the same operations in the same order" is the same code.
 #pragma once
 #include "common.h"
+#include <stdio.h>
 
 namespace selftok {
 
@@ -19,6 +21,22 @@ constexpr int W_G = BN * 16;               // weight image: linear (filled by LD
 constexpr int W_P = 4 * W_G;
 constexpr int W_BYTES = 2 * W_P;           // 16384
 constexpr int GROUP_M = 4;                 // 32 consecutive tiles (one XCD's resident set) = 4 row blocks x 8 column blocks
+
+// tile id of a work-group: XCD-contiguous renumbering (bijective), then grouped-M walk.  Work-groups are renumbered so that each
+// XCD (own L2) owns a contiguous range of tiles, walked in groups of GROUP_M row blocks, which keeps the A row panels and W column
+// panels of concurrently running work-groups in one L2.  One work-group per tile: gridDim.x = mblocks * nblocks.
+__device__ __forceinline__ void tile_of_workgroup(int mblocks, int nblocks, int& mb, int& nb)
+{
+    const int T = gridDim.x, orig = blockIdx.x;
+    const int q8 = T >> 3, r8 = T & 7, xcd = orig & 7, idx = orig >> 3;
+    const int w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int per_group = GROUP_M * nblocks;
+    const int group = w / per_group, first_m = group * GROUP_M;
+    const int gsz = (mblocks - first_m) < GROUP_M ? (mblocks - first_m) : GROUP_M;
+    const int in = w - group * per_group;
+    mb = first_m + in % gsz;
+    nb = in / gsz;
+}
 
 // GELU(tanh): 0.5 x (1 + tanh(u)) = x sigmoid(2u) = x / (1 + exp(-2u)), u = sqrt(2/pi) (x + 0.044715 x^3).  The sigmoid form needs one
 // v_exp_f32 + one v_rcp_f32 (1 ulp each) instead of ocml's tanhf (~40 VALU ops: the GELU epilogue was 8 % of the fc1 kernel) and has no
@@ -73,5 +91,47 @@ __device__ __forceinline__ void lds_dma16(const void* base, unsigned voff, unsig
 // (per-sample table: gst = 0; per-token table: gsb = 0; gate NULL: out = resid + y).  The multiply and the add are separate
 // fp32 operations, exactly as residual_ln_mod_kernel performs them on the stored y: same bits, one tensor round trip less.
 struct ResArgs { const float* resid; long ldr; const float* gate; long gsb, gst; int T; };
+
+// ---- host: the argument contract of the entry points that take a split activation (selftok_linear_f16x2_split, ..._split_k,
+// selftok_linear_f16_split and their _residual forms), `who` = the entry's name for the message.  Order of decisions: a bad shape is
+// refused; then M == 0 is SELFTOK_OK without a look at the pointers; then pointers, alignment and strides.  The caller returns the
+// result if it is not SELFTOK_OK or if M == 0, and launches otherwise.
+inline int refuse_args(const char* who, const char* what)
+{
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    set_last_error(msg);
+    return SELFTOK_EINVAL;
+}
+
+inline int check_split_linear(const char* who, const void* a_blk, const void* packed, const float* bias, const float* out, const void* out_blk,
+                              long ldo, int M, int N, int K)
+{
+    if (M < 0 || N <= 0 || K <= 0 || N % BN || K % BK) return refuse_args(who, "need N % 128 == 0 and K % 32 == 0");
+    if (M == 0) return SELFTOK_OK;
+    if (!a_blk || !packed || ((size_t)a_blk & 15) || ((size_t)out & 15) || ((size_t)out_blk & 15) || (bias && ((size_t)bias & 15))
+        || (out_blk ? out != nullptr : (!out || ldo < N || (ldo & 3))))
+        return refuse_args(who, "bad pointers/strides (a_blk, out, out_blk and bias 16-byte aligned; either out with ldo % 4 == 0, ldo >= N, or out_blk)");
+    return SELFTOK_OK;
+}
+
+inline int check_split_linear_residual(const char* who, const void* a_blk, const void* packed, const float* bias, const float* resid, long ldr,
+                                       const float* gate, long gate_stride_b, long gate_stride_t, int T, const float* out, long ldo,
+                                       int M, int N, int K)
+{
+    if (int rc = check_split_linear(who, a_blk, packed, bias, out, nullptr, ldo, M, N, K)) return rc;
+    if (M == 0) return SELFTOK_OK;
+    if (!resid || ldr < N || (ldr & 3) || T <= 0 || ((size_t)resid & 15)
+        || (gate && (((size_t)gate & 15) || (gate_stride_b & 3) || (gate_stride_t & 3))))
+        return refuse_args(who, "bad residual arguments (resid and gate 16-byte aligned, ldr >= N, ldr and the gate strides multiples of 4, T > 0)");
+    return SELFTOK_OK;
+}
+
+// split-K (the f16x2 _k entries): 2 .. 64 parts, each a whole number of k-tiles, and a workspace to put them in
+inline int check_splitk(const char* who, int K, int ksplit, const void* workspace)
+{
+    if (ksplit >= 2 && ksplit <= 64 && (K / BK) % ksplit == 0 && workspace && !((size_t)workspace & 15)) return SELFTOK_OK;
+    return refuse_args(who, "ksplit not in 2..64 / not a divisor of K / 32, or no 16-byte aligned workspace");
+}
 
 }  // namespace selftok

@@ -37,7 +37,6 @@ class MMDiTGPU(ModuleSurface):
     GEMM_MODES = ("fp32", "f16x2", "exact", "f16")
     SPLIT_MODES = ("f16x2", "f16")      # the modes that share the packed weight images, the split-activation producers and the f16x2 joint attention
     PRESPLIT = True     # f16x2 mode: producers (LN-modulate, attention, fc1+GELU) hand the next Linear its input already split
-    EXACT_FUSED_RESIDUAL_LN = True   # gemm='exact': `x + gate * Linear(.)` inside the LayerNorm pass that follows (ops.ex_res_layernorm_mod) instead of the Linear's epilogue
     SPLITK = True       # f16x2 mode, <= ops.SPLITK_MAX_ROWS rows (one .. four images): several work-groups per output tile (ops.f16x2_ksplit)
     ATTENTION_MODES = ("split", "f16")   # arithmetic of the joint attention in the split GEMM modes; 'f16' (LOSSY) only with gemm='f16'
 
@@ -152,19 +151,28 @@ class MMDiTGPU(ModuleSurface):
             assert not out_split and not isinstance(x, ops.SplitAct)
             return ops.ex_linear(x, w, b, gelu=gelu)
         if isinstance(x, ops.SplitAct):
-            assert name in self._packed, f"split activation handed to Linear {name!r}, which has no f16x2-split weight (set_gemm('f16x2') packs the block Linears)"
-            if self._single_f16(x.rows):
-                return ops.linear_f16_split(x, self._packed[name], b, w.shape[0], gelu=gelu, overflow=self.overflow, out_split=out_split)
-            return ops.linear_f16x2_split(x, self._packed[name], b, w.shape[0], gelu=gelu, overflow=self.overflow, out_split=out_split,
-                                          ksplit=self._ksplit(x.rows, w))
+            return self._lin_split(name, x, gelu=gelu, out_split=out_split)
         assert not out_split
         if self.gemm in self.SPLIT_MODES and name in self._packed:
             if self._single_f16(x.numel() // x.shape[-1]):
-                return ops.linear_f16_split(x, self._packed[name], b, w.shape[0], gelu=gelu, overflow=self.overflow)
+                return self._lin_split(name, ops.split_f16x2(x, self.overflow), gelu=gelu)
             return ops.linear_f16x2(x, self._packed[name], b, w.shape[0], gelu=gelu, overflow=self.overflow)
         if gelu:
             return ops.linear_gelu(x, w, b)
         return F.linear(x, w, b)
+
+    def _lin_split(self, name, xs, **epilogue):
+        """the packed Linear `name` on a split activation: the route (single-pass fp16 kernel, or the f16x2 kernels with which ksplit) chosen
+        here and nowhere else.  `epilogue`: gelu / out_split, or resid / gate / gate_per_sample (the fused residual update)."""
+        assert name in self._packed, f"split activation handed to Linear {name!r}, which has no f16x2-split weight (set_gemm('f16x2') packs the block Linears)"
+        w, b = self.w[name + ".weight"], self.w[name + ".bias"]
+        residual = "resid" in epilogue
+        if self._single_f16(xs.rows):
+            fn = ops.linear_f16_split_residual if residual else ops.linear_f16_split
+        else:
+            fn = ops.linear_f16x2_split_residual if residual else ops.linear_f16x2_split
+            epilogue["ksplit"] = self._ksplit(xs.rows, w)
+        return fn(xs, self._packed[name], b, w.shape[0], overflow=self.overflow, **epilogue)
 
     def _ksplit(self, rows: int, w) -> int:
         return ops.f16x2_ksplit(rows, w.shape[0], w.shape[1]) if self.SPLITK else 1
@@ -194,25 +202,14 @@ class MMDiTGPU(ModuleSurface):
             rows = x.shape[1]
             # attn.proj reads a SLICE of the concatenated attention output in the reference (non-contiguous -> at::linear = matmul + add_(bias): bias last)
             bias_last = lin_name.endswith(".attn.proj")
-            if self.EXACT_FUSED_RESIDUAL_LN:
-                # round 6: the Linear keeps its plain epilogue (the matrix pipe does not wait for 64 operand loads per lane) and the residual update rides in the
-                # LayerNorm pass behind it -- the same fp32 operations in the same order
-                y = ops.ex_linear(lin_in, wl, None if bias_last else bl)
-                return ops.ex_res_layernorm_mod(x, y, lin_bias=bl if bias_last else None, gate=gate, gate_mod=(-rows if gate_per_sample else rows),
-                                                shift=ln_kw.get("shift"), scale=ln_kw.get("scale"), per_sample=bool(ln_kw.get("per_sample", False)))
-            x = ops.ex_linear(lin_in, wl, bl, res=x, gate=gate, gate_mod=(-rows if gate_per_sample else rows), bias_last=bias_last)
-            n = ops.ex_layernorm_mod(x, shift=ln_kw.get("shift"), scale=ln_kw.get("scale"), per_sample=bool(ln_kw.get("per_sample", False)))
-            return x, n
+            # the Linear keeps its plain epilogue (the matrix pipe does not wait for 64 operand loads per lane) and the residual update rides in the
+            # LayerNorm pass behind it -- the same fp32 operations in the same order (tests/test_encoder_exact_gpu.py holds the two forms equal)
+            y = ops.ex_linear(lin_in, wl, None if bias_last else bl)
+            return ops.ex_res_layernorm_mod(x, y, lin_bias=bl if bias_last else None, gate=gate, gate_mod=(-rows if gate_per_sample else rows),
+                                            shift=ln_kw.get("shift"), scale=ln_kw.get("scale"), per_sample=bool(ln_kw.get("per_sample", False)))
         split = self._pre(consumer) if split is None else split
         if isinstance(lin_in, ops.SplitAct):
-            assert lin_name in self._packed, f"split activation handed to Linear {lin_name!r}, which has no f16x2-split weight"
-            w, b = self.w[lin_name + ".weight"], self.w[lin_name + ".bias"]
-            if self._single_f16(lin_in.rows):
-                x = ops.linear_f16_split_residual(lin_in, self._packed[lin_name], b, w.shape[0], x, gate=gate, gate_per_sample=gate_per_sample,
-                                                  overflow=self.overflow)
-            else:
-                x = ops.linear_f16x2_split_residual(lin_in, self._packed[lin_name], b, w.shape[0], x, gate=gate, gate_per_sample=gate_per_sample,
-                                                    overflow=self.overflow, ksplit=self._ksplit(lin_in.rows, w))
+            x = self._lin_split(lin_name, lin_in, resid=x, gate=gate, gate_per_sample=gate_per_sample)
             _, n = ops.residual_ln_mod(x, split=split, overflow=self.overflow, **ln_kw)
             return x, n
         return ops.residual_ln_mod(x, y=self.lin(lin_name, lin_in), gate=gate, gate_per_sample=gate_per_sample, split=split,

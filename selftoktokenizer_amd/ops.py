@@ -220,6 +220,15 @@ def code_gather_ln(ids: torch.Tensor, codebook: torch.Tensor, ln_w=None, ln_b=No
 # fused epilogues (csrc/elementwise.hip)
 # ----------------------------------------------------------------------------------------------
 
+def _table_strides(t, per_sample: bool, B: int, T: int, H: int):
+    """a modulation / gate table of a [B,T,H] tensor -- a 2-D view [T,H] (per token) or [B,H] (per_sample) with unit inner stride, or
+    None -> its (stride_b, stride_t) as the kernels take them"""
+    if t is None:
+        return 0, 0
+    assert t.dim() == 2 and t.stride(1) == 1 and t.shape == ((B, H) if per_sample else (T, H))
+    return (t.stride(0), 0) if per_sample else (0, t.stride(0))
+
+
 def residual_ln_mod(x, *, y=None, gate=None, shift=None, scale=None, per_sample=False, gate_per_sample=None,
                     want_x=True, want_n=True, eps=1e-6, split=False, overflow=None):
     """x' = x + gate*y ; n = LN(x')*(1+scale)+shift.   x,y [B,T,H].  shift/scale/gate are 2-D views
@@ -230,16 +239,10 @@ def residual_ln_mod(x, *, y=None, gate=None, shift=None, scale=None, per_sample=
     B, T, H = x.shape
     assert x.is_contiguous() and x.dtype == torch.float32
 
-    def strides(t, ps):
-        if t is None:
-            return 0, 0
-        assert t.dim() == 2 and t.stride(1) == 1 and t.shape[1] == H and t.shape[0] == (B if ps else T)
-        return (t.stride(0), 0) if ps else (0, t.stride(0))
-
     if shift is not None:
         assert scale is not None and shift.stride(0) == scale.stride(0)
-    msb, mst = strides(shift, per_sample)
-    gsb, gst = strides(gate, per_sample if gate_per_sample is None else gate_per_sample)
+    msb, mst = _table_strides(shift, per_sample, B, T, H)
+    gsb, gst = _table_strides(gate, per_sample if gate_per_sample is None else gate_per_sample, B, T, H)
     if y is not None:
         assert y.is_contiguous() and y.shape == x.shape
     x_out = torch.empty_like(x) if (y is not None and want_x) else None
@@ -297,17 +300,23 @@ def linear_f16x2_pack(weight: torch.Tensor, overflow: torch.Tensor = None) -> to
     return packed
 
 
+def _rows16(x: torch.Tensor):
+    """x [..., K] fp32 -> ([rows, K] view, row stride) that a kernel can read with 16-byte loads; a copy where the view cannot be"""
+    K = x.shape[-1]
+    x2 = x.reshape(-1, K)
+    if x2.stride(1) != 1 or (x2.shape[0] > 1 and (x2.stride(0) % 4 or x2.stride(0) < K)) or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    return x2, (x2.stride(0) if x2.shape[0] > 1 else K)
+
+
 def linear_f16x2(x: torch.Tensor, packed: torch.Tensor, bias, N: int, gelu: bool = False, overflow: torch.Tensor = None) -> torch.Tensor:
     """act(x @ W.T + bias) with W given as linear_f16x2_pack(W).  x [..., K] fp32 (rows may be strided), out [..., N] fp32."""
     _need_cuda(x, packed)
     K = x.shape[-1]
     assert x.dtype == torch.float32 and packed.numel() * 2 == 4 * N * K, "packed weight does not match (N, K)"
-    x2 = x.reshape(-1, K)
-    if x2.stride(1) != 1 or (x2.shape[0] > 1 and (x2.stride(0) % 4 or x2.stride(0) < K)) or x2.data_ptr() % 16:
-        x2 = x2.contiguous()                              # the kernel reads rows with 16-byte loads
+    x2, lda = _rows16(x)
     M = x2.shape[0]
     out = torch.empty(M, N, dtype=torch.float32, device=x.device)
-    lda = x2.stride(0) if M > 1 else K
     _lib.check(_lib.load().selftok_linear_f16x2_f32(_p(x2), lda, _p(packed), _p(bias), _p(out), N, M, N, K,
                                                     LINEAR_GELU if gelu else 0, _p(overflow), _stream()), "selftok_linear_f16x2_f32")
     return out.reshape(*x.shape[:-1], N)
@@ -344,12 +353,9 @@ def split_f16x2(x: torch.Tensor, overflow: torch.Tensor = None) -> SplitAct:
     """fp32 [..., K] -> SplitAct: hi = fp16(x), lo = fp16((x - hi) * 2^11).  The stand-alone producer, for inputs no fused producer
     makes.  `overflow` bit 0 is raised for |x| >= 65504."""
     _need_cuda(x)
-    K = x.shape[-1]
-    x2 = x.reshape(-1, K)
-    if x2.stride(1) != 1 or (x2.shape[0] > 1 and (x2.stride(0) % 4 or x2.stride(0) < K)) or x2.data_ptr() % 16:
-        x2 = x2.contiguous()
+    x2, ld = _rows16(x)
     out = SplitAct(x.shape, x.device)
-    _lib.check(_lib.load().selftok_split_f16x2_f32(_p(x2), x2.stride(0) if out.rows > 1 else K, _p(out.data), out.rows, K,
+    _lib.check(_lib.load().selftok_split_f16x2_f32(_p(x2), ld, _p(out.data), out.rows, x.shape[-1],
                                                    _p(overflow), _stream()), "selftok_split_f16x2_f32")
     return out
 
@@ -393,8 +399,37 @@ def f16x2_ksplit(M: int, N: int, K: int) -> int:
     return best
 
 
-def _splitk_ws(M: int, N: int, ksplit: int, device) -> torch.Tensor:
-    return torch.empty(ksplit * M * N, dtype=torch.float32, device=device)
+def _linear_split(xs: SplitAct, packed: torch.Tensor, bias, N: int, *, single_pass: bool, gelu: bool = False, out_split: bool = False, resid=None,
+                  gate=None, gate_per_sample: bool = False, ksplit: int = 1, overflow: torch.Tensor = None):
+    """the Linear on a split activation, every form: `single_pass` = the fp16 kernel (csrc/gemm_f16.hip; no split-K) instead of the f16x2
+    kernels (csrc/gemm_split.hip, `ksplit` parts along K); epilogue = `gelu` / `out_split`, or with `resid` [B,T,N] the fused residual
+    update resid + gate * y.  Returns fp32 [..., N], a SplitAct [..., N], or a tensor like resid."""
+    _need_cuda(xs.data, packed, resid)
+    K = xs.shape[-1]
+    assert packed.numel() * 2 == 4 * N * K, "packed weight does not match (N, K)"
+    assert not (single_pass and ksplit != 1), "the single-pass fp16 kernel has no split-K variant"
+    M, lead = xs.rows, xs.shape[:-1]
+    lib = _lib.load()
+    name = "selftok_linear_f16_split" if single_pass else "selftok_linear_f16x2_split"
+    tail = (_p(overflow), _stream())
+    if not single_pass:                                   # the _k entries; ksplit == 1 is their single launch
+        ws = torch.empty(ksplit * M * N, dtype=torch.float32, device=xs.device) if (ksplit > 1 and M > 0) else None
+        tail = (ksplit, _p(ws)) + tail
+    if resid is not None:
+        assert not gelu and not out_split
+        assert resid.dim() == 3 and resid.is_contiguous() and resid.dtype == torch.float32 and resid.shape[-1] == N
+        B, T, _ = resid.shape
+        assert M == B * T
+        gsb, gst = _table_strides(gate, gate_per_sample, B, T, N)
+        out = torch.empty_like(resid)
+        name += "_residual" if single_pass else "_residual_k"
+        _lib.check(getattr(lib, name)(_p(xs.data), _p(packed), _p(bias), _p(resid), N, _p(gate), gsb, gst, T, _p(out), N, M, N, K, *tail), name)
+        return out
+    out = SplitAct((*lead, N), xs.device) if out_split else torch.empty(M, N, dtype=torch.float32, device=xs.device)
+    name += "" if single_pass else "_k"
+    _lib.check(getattr(lib, name)(_p(xs.data), _p(packed), _p(bias), None if out_split else _p(out), _p(out.data) if out_split else None, N, M, N, K,
+                                  LINEAR_GELU if gelu else 0, *tail), name)
+    return out if out_split else out.reshape(*lead, N)
 
 
 def linear_f16x2_split(xs: SplitAct, packed: torch.Tensor, bias, N: int, gelu: bool = False, overflow: torch.Tensor = None,
@@ -403,22 +438,7 @@ def linear_f16x2_split(xs: SplitAct, packed: torch.Tensor, bias, N: int, gelu: b
     [..., N] for the next Linear.  Same results as linear_f16x2 on the fp32 tensor.  ksplit > 1 (small M, `f16x2_ksplit`): that many
     work-groups per output tile + a reduction launch; deterministic, equal to the single-pass result up to fp32 rounding of the
     partial sums (selftok_linear_f16x2_split_k)."""
-    _need_cuda(xs.data, packed)
-    K = xs.shape[-1]
-    assert packed.numel() * 2 == 4 * N * K, "packed weight does not match (N, K)"
-    M, lead = xs.rows, xs.shape[:-1]
-    lib = _lib.load()
-    flags = LINEAR_GELU if gelu else 0
-    ws = _splitk_ws(M, N, ksplit, xs.device) if (ksplit > 1 and M > 0) else None
-    if out_split:
-        out = SplitAct((*lead, N), xs.device)
-        _lib.check(lib.selftok_linear_f16x2_split_k(_p(xs.data), _p(packed), _p(bias), None, _p(out.data), N, M, N, K, flags, ksplit, _p(ws), _p(overflow), _stream()),
-                   "selftok_linear_f16x2_split_k")
-        return out
-    out = torch.empty(M, N, dtype=torch.float32, device=xs.device)
-    _lib.check(lib.selftok_linear_f16x2_split_k(_p(xs.data), _p(packed), _p(bias), _p(out), None, N, M, N, K, flags, ksplit, _p(ws), _p(overflow), _stream()),
-               "selftok_linear_f16x2_split_k")
-    return out.reshape(*lead, N)
+    return _linear_split(xs, packed, bias, N, single_pass=False, gelu=gelu, out_split=out_split, ksplit=ksplit, overflow=overflow)
 
 
 def linear_f16x2_split_residual(xs: SplitAct, packed: torch.Tensor, bias, N: int, resid: torch.Tensor, gate=None,
@@ -426,22 +446,7 @@ def linear_f16x2_split_residual(xs: SplitAct, packed: torch.Tensor, bias, N: int
     """resid + gate * (xs @ W.T + bias): linear_f16x2_split with the block's residual update fused into the epilogue.
     resid [B,T,N] fp32 contiguous; gate a 2-D view [T,N] (per token) or [B,N] (gate_per_sample) with unit inner stride, or None.
     Bit-identical to residual_ln_mod(resid, y=linear_f16x2_split(...), gate=gate)[0]."""
-    _need_cuda(xs.data, packed, resid)
-    K = xs.shape[-1]
-    assert packed.numel() * 2 == 4 * N * K
-    assert resid.dim() == 3 and resid.is_contiguous() and resid.dtype == torch.float32 and resid.shape[-1] == N
-    B, T, _ = resid.shape
-    M = B * T
-    assert xs.rows == M
-    gsb = gst = 0
-    if gate is not None:
-        assert gate.dim() == 2 and gate.stride(1) == 1 and gate.shape == ((B, N) if gate_per_sample else (T, N))
-        gsb, gst = (gate.stride(0), 0) if gate_per_sample else (0, gate.stride(0))
-    out = torch.empty_like(resid)
-    ws = _splitk_ws(M, N, ksplit, resid.device) if (ksplit > 1 and M > 0) else None
-    _lib.check(_lib.load().selftok_linear_f16x2_split_residual_k(_p(xs.data), _p(packed), _p(bias), _p(resid), N, _p(gate), gsb, gst, T,
-                                                             _p(out), N, M, N, K, ksplit, _p(ws), _p(overflow), _stream()), "selftok_linear_f16x2_split_residual_k")
-    return out
+    return _linear_split(xs, packed, bias, N, single_pass=False, resid=resid, gate=gate, gate_per_sample=gate_per_sample, ksplit=ksplit, overflow=overflow)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -458,44 +463,14 @@ def linear_f16_split(xs, packed: torch.Tensor, bias, N: int, gelu: bool = False,
     f16x2 mode holds -- only the hi planes of both are read.  Returns fp32 [..., N], or with out_split a SplitAct with both planes.
     On fp16-representable operands the result equals linear_f16x2_split's.  There is no split-K variant of this kernel: callers
     keep row counts <= SPLITK_MAX_ROWS on linear_f16x2_split(..., ksplit=f16x2_ksplit(...)) (MMDiTGPU.lin does)."""
-    xs = _as_split(xs, overflow)
-    _need_cuda(xs.data, packed)
-    K = xs.shape[-1]
-    assert packed.numel() * 2 == 4 * N * K, "packed weight does not match (N, K)"
-    M, lead = xs.rows, xs.shape[:-1]
-    lib = _lib.load()
-    flags = LINEAR_GELU if gelu else 0
-    if out_split:
-        out = SplitAct((*lead, N), xs.device)
-        _lib.check(lib.selftok_linear_f16_split(_p(xs.data), _p(packed), _p(bias), None, _p(out.data), N, M, N, K, flags, _p(overflow), _stream()),
-                   "selftok_linear_f16_split")
-        return out
-    out = torch.empty(M, N, dtype=torch.float32, device=xs.device)
-    _lib.check(lib.selftok_linear_f16_split(_p(xs.data), _p(packed), _p(bias), _p(out), None, N, M, N, K, flags, _p(overflow), _stream()),
-               "selftok_linear_f16_split")
-    return out.reshape(*lead, N)
+    return _linear_split(_as_split(xs, overflow), packed, bias, N, single_pass=True, gelu=gelu, out_split=out_split, overflow=overflow)
 
 
 def linear_f16_split_residual(xs, packed: torch.Tensor, bias, N: int, resid: torch.Tensor, gate=None,
                               gate_per_sample: bool = False, overflow: torch.Tensor = None) -> torch.Tensor:
     """resid + gate * linear_f16_split(xs): the fused residual epilogue of linear_f16x2_split_residual (same operations, same order)
     on the single-pass fp16 product.  Arguments as there; `xs` may be an fp32 tensor."""
-    xs = _as_split(xs, overflow)
-    _need_cuda(xs.data, packed, resid)
-    K = xs.shape[-1]
-    assert packed.numel() * 2 == 4 * N * K
-    assert resid.dim() == 3 and resid.is_contiguous() and resid.dtype == torch.float32 and resid.shape[-1] == N
-    B, T, _ = resid.shape
-    M = B * T
-    assert xs.rows == M
-    gsb = gst = 0
-    if gate is not None:
-        assert gate.dim() == 2 and gate.stride(1) == 1 and gate.shape == ((B, N) if gate_per_sample else (T, N))
-        gsb, gst = (gate.stride(0), 0) if gate_per_sample else (0, gate.stride(0))
-    out = torch.empty_like(resid)
-    _lib.check(_lib.load().selftok_linear_f16_split_residual(_p(xs.data), _p(packed), _p(bias), _p(resid), N, _p(gate), gsb, gst, T,
-                                                             _p(out), N, M, N, K, _p(overflow), _stream()), "selftok_linear_f16_split_residual")
-    return out
+    return _linear_split(_as_split(xs, overflow), packed, bias, N, single_pass=True, resid=resid, gate=gate, gate_per_sample=gate_per_sample, overflow=overflow)
 
 
 def silu(x):

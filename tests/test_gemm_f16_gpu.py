@@ -46,6 +46,13 @@ def _raw(fn_name, xs, packed, bias, out, out_blk, ldo, M, N, K, flags=0, overflo
     return getattr(_lib.load(), fn_name)(p(xs), p(packed), p(bias), p(out), p(out_blk), ldo, M, N, K, flags, p(overflow), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
 
 
+def _raw_k(xs, packed, bias, out, out_blk, ldo, M, N, K, ksplit, ws, flags=0):
+    """selftok_linear_f16x2_split_k: the plain entry's arguments + (ksplit, workspace)"""
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    return _lib.load().selftok_linear_f16x2_split_k(p(xs), p(packed), p(bias), p(out), p(out_blk), ldo, M, N, K, flags, ksplit, p(ws), None,
+                                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
 @pytest.mark.parametrize("K", KS)
 def test_equals_the_f16x2_kernel_on_fp16_operands_every_epilogue(K):
     """every M x N of the table at this K: plain / no bias / GELU / split output / the three residual forms, each EQUAL to the f16x2 single-pass
@@ -155,6 +162,7 @@ def test_range_flag_empty_input_and_refusals():
     out = torch.empty(300, 128, device="cuda")
     oblk = ops.SplitAct((300, 128), "cuda").data
     EINVAL = -1
+    ws = torch.empty(2 * 300 * 128, device="cuda")                          # a valid workspace for ksplit = 2: the split-K entries refuse these rows for the plain contract
     for what, args in (("N % 128", (xs.data, packed, b, out, None, 100, 300, 100, 64)), ("K % 32", (xs.data, packed, b, out, None, 128, 300, 128, 48)),
                        ("no activations", (None, packed, b, out, None, 128, 300, 128, 64)), ("no weights", (xs.data, None, b, out, None, 128, 300, 128, 64)),
                        ("no output", (xs.data, packed, b, None, None, 128, 300, 128, 64)), ("both outputs", (xs.data, packed, b, out, oblk, 128, 300, 128, 64)),
@@ -162,14 +170,27 @@ def test_range_flag_empty_input_and_refusals():
                        ("M < 0", (xs.data, packed, b, out, None, 128, -1, 128, 64)), ("unaligned bias", (xs.data, packed, b[1:], out, None, 128, 300, 128, 64))):
         assert _raw("selftok_linear_f16_split", *args) == EINVAL, what
         assert _raw("selftok_linear_f16x2_split", *args) == EINVAL, what + " (the f16x2 entry refuses it too)"
+        assert _raw_k(*args, 2, ws) == EINVAL, what + " (and the f16x2 split-K entry)"
         assert b"linear_f16" in _lib.load().selftok_last_error()
     lib, p = _lib.load(), lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
     res = torch.zeros(300, 128, device="cuda")
     for what, (x_, w_, r_, ldr, T, M_, N_, K_) in (("N % 128", (xs.data, packed, res, 128, 300, 300, 100, 64)), ("K % 32", (xs.data, packed, res, 128, 300, 300, 128, 48)),
                                                    ("no residual", (xs.data, packed, None, 128, 300, 300, 128, 64)), ("ldr < N", (xs.data, packed, res, 64, 300, 300, 128, 64)),
                                                    ("T = 0", (xs.data, packed, res, 128, 0, 300, 128, 64)), ("no activations", (None, packed, res, 128, 300, 300, 128, 64))):
-        for name in ("selftok_linear_f16_split_residual", "selftok_linear_f16x2_split_residual"):
-            assert getattr(lib, name)(p(x_), p(w_), p(b), p(r_), ldr, None, 0, 0, T, p(out), 128, M_, N_, K_, None, None) == EINVAL, (what, name)
+        for name, sk in (("selftok_linear_f16_split_residual", ()), ("selftok_linear_f16x2_split_residual", ()), ("selftok_linear_f16x2_split_residual_k", (2, p(ws)))):
+            assert getattr(lib, name)(p(x_), p(w_), p(b), p(r_), ldr, None, 0, 0, T, p(out), 128, M_, N_, K_, *sk, None, None) == EINVAL, (what, name)
+    # what the split-K entries refuse on top: K / 32 = 6 k-tiles, so 4 is no divisor; more than 64 parts; no workspace; one that is not 16-byte aligned
+    a6, w6, b6 = _data(300, 128, 192)
+    xs6, packed6 = ops.split_f16x2(a6), ops.linear_f16x2_pack(w6)
+    ws6 = torch.empty(4 * 300 * 128 + 4, device="cuda")
+    plain_k = lambda ks, w_: _raw_k(xs6.data, packed6, b6, out, None, 128, 300, 128, 192, ks, w_)
+    resid_k = lambda ks, w_: lib.selftok_linear_f16x2_split_residual_k(p(xs6.data), p(packed6), p(b6), p(res), 128, None, 0, 0, 300, p(out), 128, 300, 128, 192, ks, p(w_), None, None)
+    for what, ks, w_ in (("ksplit = 4 does not divide K / 32 = 6", 4, ws6), ("ksplit = 65", 65, ws6), ("no workspace", 2, None), ("workspace 4 bytes off", 2, ws6[1:])):
+        assert plain_k(ks, w_) == EINVAL, what
+        assert b"linear_f16x2_split_k" in lib.selftok_last_error()
+        assert resid_k(ks, w_) == EINVAL, what + " (residual)"
+        assert b"linear_f16x2_split_residual_k" in lib.selftok_last_error()
+    assert plain_k(2, ws6) == 0 and resid_k(2, ws6) == 0, "ksplit = 2 with its workspace is the legal call the rows above depart from"
     torch.cuda.synchronize()
 
 
@@ -238,6 +259,59 @@ def test_velocity_error_against_the_reference_is_that_of_fp16_rounded_operands(s
         pass
     route = err["fp32 on fp16-rounded operands"]
     assert err["f16"][0] <= 1.25 * route[0] and err["f16"][1] <= 1.25 * route[1], (err["f16"], route)
+
+
+def test_block_linear_routes_by_mode_and_row_count(sd, monkeypatch):
+    """which ops entry MMDiTGPU.lin and ._res_ln reach, and with which ksplit: the five Linear entries, as mmdit sees them, are replaced by recorders that
+    call through.  16 rows (one chunk) and 1040 (the first chunk count above SPLITK_MAX_ROWS) of the model's width 1536; split input to `lin` plain,
+    `lin(gelu, out_split)` on mlp.fc1 and `_res_ln` with a per-sample gate on attn.proj, and fp32 input to `lin` (the PRESPLIT = False reference form).
+    Rows <= SPLITK_MAX_ROWS land on the f16x2 entries in both modes with ksplit = f16x2_ksplit(rows, N, K); above, on the single-pass fp16 entries in
+    "f16" only."""
+    from selftoktokenizer_amd import mmdit
+    H = 1536
+    dev = torch.device("cuda", torch.cuda.current_device())
+    d = mmdit.MMDiTGPU(sd, dev, 512)
+    calls = []
+    for fn in ("linear_f16x2", "linear_f16x2_split", "linear_f16x2_split_residual", "linear_f16_split", "linear_f16_split_residual"):
+        def recorder(*a, _fn=fn, _real=getattr(ops, fn), **kw):
+            calls.append((_fn, kw.get("ksplit")))
+            return _real(*a, **kw)
+        monkeypatch.setattr(mmdit.ops, fn, recorder)
+    blk = "model.joint_blocks.3.x_block."
+    g = torch.Generator(device="cuda").manual_seed(11)
+    assert d.SPLITK and ops.SPLITK_MAX_ROWS == 1024
+    for mode in ("f16x2", "f16"):
+        assert d.set_gemm(mode) == mode
+        for rows in (16, 1040):
+            B, T = 2, rows // 2
+            x = torch.randn(B, T, H, device="cuda", generator=g)
+            tab = torch.randn(B, 3 * H, device="cuda", generator=g)
+            single = mode == "f16" and rows > ops.SPLITK_MAX_ROWS
+            ks = lambda name: ops.f16x2_ksplit(rows, *d.w[blk + name + ".weight"].shape)
+            tag = f"{mode}, {rows} rows"
+
+            def reached(run):
+                del calls[:]
+                out = run()
+                torch.cuda.synchronize()
+                return list(calls), out
+
+            got, y = reached(lambda: d.lin(blk + "attn.qkv", ops.split_f16x2(x)))
+            assert got == [("linear_f16_split", None) if single else ("linear_f16x2_split", ks("attn.qkv"))], tag + ": lin, split input"
+            assert tuple(y.shape) == (B, T, 3 * H)
+            got, y = reached(lambda: d.lin(blk + "attn.qkv", x))
+            assert got == [("linear_f16_split", None) if single else ("linear_f16x2", None)], tag + ": lin, fp32 input"
+            assert tuple(y.shape) == (B, T, 3 * H)
+            got, y = reached(lambda: d.lin(blk + "mlp.fc1", ops.split_f16x2(x), gelu=True, out_split=True))
+            assert got == [("linear_f16_split", None) if single else ("linear_f16x2_split", ks("mlp.fc1"))], tag + ": lin(gelu, out_split) on mlp.fc1"
+            assert isinstance(y, ops.SplitAct) and y.shape == (B, T, 4 * H)
+            got, (x2, n) = reached(lambda: d._res_ln(blk + "mlp.fc1", x, blk + "attn.proj", ops.split_f16x2(x), gate=tab[:, 2 * H:], gate_per_sample=True,
+                                                     shift=tab[:, :H], scale=tab[:, H:2 * H], per_sample=True))
+            assert got == [("linear_f16_split_residual", None) if single else ("linear_f16x2_split_residual", ks("attn.proj"))], tag + ": _res_ln on attn.proj"
+            assert tuple(x2.shape) == (B, T, H) and isinstance(n, ops.SplitAct)
+            if rows <= ops.SPLITK_MAX_ROWS:
+                assert ks("attn.qkv") > 1, "16 rows are the split-K regime"
+    assert int(d.overflow.item()) == 0
 
 
 # ---- pipeline level ----------------------------------------------------------------------------------------------------------------------
