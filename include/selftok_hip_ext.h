@@ -137,6 +137,40 @@ int selftok_linear_f16_split_residual(const void* a_blk, const void* packed, con
  * message; B == 0 or no query row returns 0 without a launch. */
 int selftok_attn_f16(const selftok_attn_desc* desc, const unsigned* kmask, long kmask_bs, hipStream_t stream);
 
+/* ---- LPIPS stages (AlexNet backbone): fp32 convolution, max-pool, input stage, fp64 distance stage ------------
+ * The kernels of selftoktokenizer_amd/lpips.py (LPIPS_DEFINITION states the metric; csrc/lpips.hip states the arithmetic).  Activations
+ * are channels-last fp32 [N, H, W, C], contiguous.  Every refusal (null pointer, a shape without an output pixel, an element count
+ * >= 2^31, a short workspace) is decided on the host before any launch and returns SELFTOK_EINVAL with a message.
+ *
+ * selftok_lpips_conv2d_f32: cross-correlation with zero padding, + bias (NULL: none), + ReLU when relu != 0, in [N, H, W, Cin] ->
+ *   out [N, OH, OW, Cout], OH = (H + 2 pad - KH) / stride + 1 (floor).  `packed` is the weight [Cout, Cin, KH, KW] re-laid as
+ *   [KP][CoutP] fp32 with row k = (kh * KW + kw) * Cin + ci, KP = K rounded up to 16, CoutP = Cout rounded up to 64, the padding
+ *   zero-filled; selftok_lpips_conv2d_packed_floats returns KP * CoutP (0 with the error set when refused).  fp32 operands and
+ *   accumulation on v_mfma_f32_32x32x2_f32: every output is eight fmaf chains from +0.0f (chain j: the taps with k mod 16 in {2j, 2j + 1},
+ *   ascending; a padding tap is an exact zero, never a neighbour's value) added as a fixed fp32 tree, then one fp32 addition of the bias,
+ *   then v < 0 ? 0 : v.  An output depends on its own image alone.
+ *   0 <= pad < KH, KW;  `in` and `packed` 16-byte aligned.
+ * selftok_lpips_maxpool3s2_f32: 3 x 3 windows, stride 2, no padding, floor mode: [N, H, W, C] -> [N, (H - 3) / 2 + 1, (W - 3) / 2 + 1, C];
+ *   a NaN in a window is the window's result.  H, W >= 3.
+ * selftok_lpips_input: recon [B, 3, H, W] in [0, 1] and orig [B, 3, H, W] (bf16 or fp32 each, NCHW) -> out [2B, H, W, 3], recon images
+ *   first: x = float32(v) * 2 - 1 (two fp32 roundings; a signed original is taken as it is), or with quantize != 0
+ *   x = byte / 255 * 2 - 1 in fp32 of the byte selftok_img_metrics takes (recon in its own type; the original from
+ *   o = (v + 1) / 2 when signed, as fp32), then the scaling layer (x - shift_c) / scale_c in fp32 with a true division,
+ *   shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450).  H, W >= 31: below that a tap of the network has no pixel.
+ * selftok_lpips_distance: feat [2B, npix, C] (images b and b + B are pair b) and w [C] -> out[b] (fp64, device) = the tap's contribution
+ *   mean_p sum_c w_c (f0_c / n0 - f1_c / n1)^2, n = sqrt(sum_c f_c^2) + 1e-10, every operation in fp64 and rounded on its own, sums in a
+ *   fixed order (csrc/lpips.hip), no atomics: out[b] is a function of pair b alone.  accumulate != 0: out[b] += instead of =.
+ *   Workspace (one fp64 per 64-pixel tile and pair) from the query; 0 with the error set when B or npix is refused.  B <= 65535. */
+size_t selftok_lpips_conv2d_packed_floats(int Cin, int Cout, int KH, int KW);
+int selftok_lpips_conv2d_f32(const float* in, const float* packed, const float* bias, float* out, int N, int H, int W, int Cin, int Cout,
+                             int KH, int KW, int stride, int pad, int relu, hipStream_t stream);
+int selftok_lpips_maxpool3s2_f32(const float* in, float* out, int N, int H, int W, int C, hipStream_t stream);
+int selftok_lpips_input(const void* recon, int recon_bf16, const void* orig, int orig_bf16, int orig_signed, int quantize, float* out,
+                        int B, int H, int W, hipStream_t stream);
+size_t selftok_lpips_distance_workspace_bytes(int B, int npix);
+int selftok_lpips_distance(const float* feat, const float* w, double* out, void* workspace, size_t workspace_bytes, int B, int npix, int C,
+                           int accumulate, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

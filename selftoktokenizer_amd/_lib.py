@@ -96,6 +96,12 @@ EXT_SIGNATURES = {
     "selftok_linear_f16_split": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _vp]),
     "selftok_linear_f16_split_residual": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _l, _l, _i, _vp, _l, _i, _i, _i, _vp, _vp]),
     "selftok_attn_f16": (_i, [_vp, _vp, _l, _vp]),
+    "selftok_lpips_conv2d_packed_floats": (_sz, [_i, _i, _i, _i]),
+    "selftok_lpips_conv2d_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
+    "selftok_lpips_maxpool3s2_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "selftok_lpips_input": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    "selftok_lpips_distance_workspace_bytes": (_sz, [_i, _i]),
+    "selftok_lpips_distance": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
 }
 
 

@@ -65,18 +65,21 @@ def metrics_each(recon: torch.Tensor, original: torch.Tensor, quantize: bool = F
 
 def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int, batch: int = 64, decoders: Sequence[str] = ("diffusion",),
              noise_fn: Optional[Callable[[int, int], torch.Tensor]] = None, seed: Optional[int] = 1234, renderer_pipe=None, verbose: bool = False,
-             metrics: Sequence[str] = ("psnr",), metrics_u8: bool = False) -> Dict:
+             metrics: Sequence[str] = ("psnr",), metrics_u8: bool = False, lpips=None) -> Dict:
     """PSNR of `n_images` images through `pipe` (and `renderer_pipe` for the one-step decoder), this rank's contiguous shard of them
     (dist.shard_range) in batches of `batch`; per-image values are gathered to every rank (one all_gather_into_tensor per decoder at the end).
     load_batch(lo, hi) -> float tensor [hi-lo, 3, H, W] in [-1, 1] (host or device).  noise_fn(lo, hi) -> [hi-lo, 16, h, w] replaces the
     reference's `torch.randn` draw (global CPU generator, seeded here with `seed` + rank when given).
     metrics (extension): ("psnr",) is the host route above.  With "ssim" in it both figures come from one device call per batch (ops.image_metrics, no host
     copy of the images, one read of the [n, 2] results at the end): every decoder's dict gains `ssim_mean` / `ssim_each` and the result says which SSIM it is
-    (`metric_definition`).  metrics_u8: take both on the bytes `save_image` would write (needs "ssim": the host route has no such mode)."""
-    bad = [m for m in metrics if m not in ("psnr", "ssim")]
+    (`metric_definition`).  metrics_u8: take both on the bytes `save_image` would write (needs "ssim": the host route has no such mode).
+    "lpips" with `lpips=` an lpips.LpipsNet (the weights are not shipped, so there is no default network): the device route as for "ssim", every decoder's dict
+    also gains `lpips_mean` / `lpips_each` and `metric_definition["lpips"]` states the definition and where the weights came from; metrics_u8 applies to it too."""
+    with_lpips = "lpips" in metrics and lpips is not None
+    bad = [m for m in metrics if m not in ("psnr", "ssim") and not (m == "lpips" and with_lpips)]
     if bad or not metrics:
-        raise ValueError(f"metrics {tuple(metrics)!r}: expected a non-empty subset of ('psnr', 'ssim')")
-    on_device = "ssim" in metrics
+        raise ValueError(f"metrics {tuple(metrics)!r}: expected a non-empty subset of ('psnr', 'ssim')" + (", or 'lpips' together with lpips=<LpipsNet>" if "lpips" in bad else ""))
+    on_device = "ssim" in metrics or with_lpips
     if metrics_u8 and not on_device:
         raise ValueError("metrics_u8 needs 'ssim' in `metrics` (the device route); the host PSNR route is the float one")
     world, rank = D.world_size(), D.rank()       # the dist module's view: sharding and the gather below must agree (ADVICE r5)
@@ -102,7 +105,10 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
                 raise ValueError(f"decoder {d!r}: expected 'diffusion' or 'renderer'")
             if on_device:
                 from . import ops
-                vals[d].append(ops.image_metrics(rec.detach(), imgs, original_signed=True, quantize=metrics_u8))      # [b, 2] fp64, stays on the device
+                m = ops.image_metrics(rec.detach(), imgs, original_signed=True, quantize=metrics_u8)      # [b, 2] fp64, stays on the device
+                if with_lpips:
+                    m = torch.cat([m, lpips(rec.detach(), imgs, original_signed=True, quantize=metrics_u8)[:, None]], dim=1)      # [b, 3]
+                vals[d].append(m)
             else:
                 vals[d].append(psnr_each(rec, imgs))
         if verbose and rank == 0:
@@ -111,17 +117,22 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     out = {"images": int(n_images), "ranks": world, "batch": int(batch), "shard": [int(lo), int(hi)]}
     for d in decoders:
         if on_device:
-            mine = torch.cat(vals[d]) if vals[d] else torch.zeros(0, 2, dtype=torch.float64, device=pipe.device)
+            mine = torch.cat(vals[d]) if vals[d] else torch.zeros(0, 3 if with_lpips else 2, dtype=torch.float64, device=pipe.device)
             allv = D.all_gather_rows(mine, counts).cpu().numpy()
             ssim, psnr = allv[:, 0], psnr_of_mse(allv[:, 1])
             out[d] = {"psnr_mean_dB": float(psnr.mean()) if psnr.size else float("nan"), "psnr_each_dB": [round(float(v), 6) for v in psnr],
                       "ssim_mean": float(ssim.mean()) if ssim.size else float("nan"), "ssim_each": [round(float(v), 9) for v in ssim]}
+            if with_lpips:
+                out[d].update({"lpips_mean": float(allv[:, 2].mean()) if ssim.size else float("nan"), "lpips_each": [round(float(v), 9) for v in allv[:, 2]]})
             continue
         mine = torch.from_numpy(np.concatenate(vals[d]) if vals[d] else np.zeros(0)).to(torch.float64)
         allv = D.all_gather_rows(mine.to(pipe.device), counts).cpu().numpy()      # returns `mine` when there is no exchange to perform
         out[d] = {"psnr_mean_dB": float(allv.mean()) if allv.size else float("nan"), "psnr_each_dB": [round(float(v), 6) for v in allv]}
     if on_device:
         out["metric_definition"] = dict(SSIM_DEFINITION, on="u8" if metrics_u8 else "float")
+        if with_lpips:
+            from .lpips import LPIPS_DEFINITION
+            out["metric_definition"]["lpips"] = dict(LPIPS_DEFINITION, weights=lpips.source)
     out["token_ids_first_image"] = ids_all[0][0, :8].tolist() if ids_all else []
     return out
 

@@ -1165,3 +1165,116 @@ def image_metrics(recon: torch.Tensor, original: torch.Tensor, original_signed: 
     _lib.check(lib.selftok_img_metrics(_p(recon), int(recon.dtype == torch.bfloat16), _p(original), int(original.dtype == torch.bfloat16), int(bool(original_signed)),
                                        int(bool(quantize)), win.ctypes.data, _p(out), _p(ws), ws.numel(), B, H, W, _stream()), "selftok_img_metrics")
     return out
+
+
+# ---- LPIPS stages (csrc/lpips.hip, include/selftok_hip_ext.h): channels-last fp32 activations [N, H, W, C] ----
+def _lpips_f32(name: str, t: torch.Tensor, dim: int) -> torch.Tensor:
+    if t.dtype != torch.float32 or t.dim() != dim:
+        raise _lib.SelftokHipError(f"lpips: `{name}` must be a float32 tensor of {dim} dimensions, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def lpips_pack_conv_weight(weight: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, KH, KW] fp32 (any device) -> the [KP, CoutP] image lpips_conv2d reads: row k = (kh * KW + kw) * Cin + ci, K rounded up to 16 and Cout to 64
+    with zeros.  A re-layout only (no arithmetic), done once when a network is built."""
+    if weight.dim() != 4:
+        raise _lib.SelftokHipError(f"lpips_pack_conv_weight: expected [Cout, Cin, KH, KW], got {tuple(weight.shape)}")
+    Cout, Cin, KH, KW = weight.shape
+    n = _lib.load().selftok_lpips_conv2d_packed_floats(Cin, Cout, KH, KW)
+    if n == 0:
+        _lib.check(-1, "selftok_lpips_conv2d_packed_floats")
+    K, CP = KH * KW * Cin, -(-Cout // 64) * 64
+    out = torch.zeros(n // CP, CP, dtype=torch.float32, device=weight.device)
+    out[:K, :Cout] = weight.detach().float().permute(2, 3, 1, 0).reshape(K, Cout)
+    return out
+
+
+def lpips_conv2d(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], Cout: int, KH: int, KW: int, stride: int, pad: int, relu: bool,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [N, H, W, Cin] fp32 channels-last, `packed` from lpips_pack_conv_weight -> [N, OH, OW, Cout]: per output eight k-ordered fmaf chains on the
+    f32-input MFMA (chain j takes the taps with k mod 16 in {2j, 2j + 1}), added as ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7)), + bias, + ReLU
+    (include/selftok_hip_ext.h)."""
+    _need_cuda(x, packed, bias, out)
+    x, packed = _lpips_f32("x", x, 4), _lpips_f32("packed", packed, 2)
+    bias = None if bias is None else _lpips_f32("bias", bias, 1)
+    N, H, W, Cin = x.shape
+    lib = _lib.load()
+    if packed.numel() != lib.selftok_lpips_conv2d_packed_floats(Cin, Cout, KH, KW) or (bias is not None and bias.numel() != Cout):
+        raise _lib.SelftokHipError(f"lpips_conv2d: packed weight of {packed.numel()} floats / bias do not belong to Cin {Cin}, Cout {Cout}, {KH} x {KW}")
+    OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    if out is None:
+        out = torch.empty(N, max(OH, 0), max(OW, 0), Cout, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (N, OH, OW, Cout) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"lpips_conv2d: `out` must be a contiguous float32 {(N, OH, OW, Cout)}, got {out.dtype} {tuple(out.shape)}")
+    _lib.check(lib.selftok_lpips_conv2d_f32(_p(x), _p(packed), _p(bias), _p(out), N, H, W, Cin, Cout, KH, KW, stride, pad, int(bool(relu)), _stream()),
+               "selftok_lpips_conv2d_f32")
+    return out
+
+
+def lpips_maxpool3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [N, H, W, C] fp32 channels-last -> [N, (H - 3) // 2 + 1, (W - 3) // 2 + 1, C]: 3 x 3 windows, stride 2, floor mode, no padding"""
+    _need_cuda(x, out)
+    x = _lpips_f32("x", x, 4)
+    N, H, W, C = x.shape
+    shape = (N, max((H - 3) // 2 + 1, 0), max((W - 3) // 2 + 1, 0), C)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"lpips_maxpool3s2: `out` must be a contiguous float32 {shape}, got {out.dtype} {tuple(out.shape)}")
+    _lib.check(_lib.load().selftok_lpips_maxpool3s2_f32(_p(x), _p(out), N, H, W, C, _stream()), "selftok_lpips_maxpool3s2_f32")
+    return out
+
+
+def lpips_input(recon: torch.Tensor, original: torch.Tensor, original_signed: bool = True, quantize: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """recon [B, 3, H, W] in [0, 1] and original [B, 3, H, W] (bf16 or fp32 each) -> the scaling layer's output [2B, H, W, 3] fp32, recon images first"""
+    for name, t in (("recon", recon), ("original", original)):
+        if t.dtype not in (torch.bfloat16, torch.float32):
+            raise _lib.SelftokHipError(f"lpips_input: `{name}` dtype {t.dtype}: expected bfloat16 or float32")
+    if recon.dim() != 4 or recon.shape[1] != 3 or tuple(original.shape) != tuple(recon.shape):
+        raise _lib.SelftokHipError(f"lpips_input: expected two [B, 3, H, W] tensors of one shape, got {tuple(recon.shape)} and {tuple(original.shape)}")
+    _need_cuda(recon, original, out)
+    recon, original = recon.contiguous(), original.contiguous()
+    B, _, H, W = recon.shape
+    if out is None:
+        out = torch.empty(2 * B, H, W, 3, dtype=torch.float32, device=recon.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (2 * B, H, W, 3) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"lpips_input: `out` must be a contiguous float32 {(2 * B, H, W, 3)}, got {out.dtype} {tuple(out.shape)}")
+    _lib.check(_lib.load().selftok_lpips_input(_p(recon), int(recon.dtype == torch.bfloat16), _p(original), int(original.dtype == torch.bfloat16),
+                                               int(bool(original_signed)), int(bool(quantize)), _p(out), B, H, W, _stream()), "selftok_lpips_input")
+    return out
+
+
+_LPIPS_WS = {}           # (device index, stream handle) -> workspace tensors, largest last (the `_IMG_METRICS_WS` rules)
+
+
+def lpips_workspace(device, nbytes: int) -> torch.Tensor:
+    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream))
+    held = _LPIPS_WS.setdefault(key, [])
+    if not held or held[-1].numel() < nbytes:
+        held.append(torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device))
+    return held[-1]
+
+
+def lpips_distance(feat: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """feat [2B, h, w, C] fp32 channels-last (images b and b + B are pair b), w [C] fp32 -> fp64 [B]: the tap's contribution to LPIPS, fp64 from the features on.
+    accumulate: added to `out` instead of stored."""
+    _need_cuda(feat, w, out, workspace)
+    feat, w = _lpips_f32("feat", feat, 4), _lpips_f32("w", w, 1)
+    N, h, wd, C = feat.shape
+    if N < 2 or N % 2 or w.numel() != C:
+        raise _lib.SelftokHipError(f"lpips_distance: expected feat [2B, h, w, C] and w [C], got {tuple(feat.shape)} and {tuple(w.shape)}")
+    B = N // 2
+    if out is None:
+        if accumulate:
+            raise _lib.SelftokHipError("lpips_distance: accumulate needs `out`")
+        out = torch.empty(B, dtype=torch.float64, device=feat.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B,) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"lpips_distance: `out` must be a contiguous float64 [{B}], got {out.dtype} {tuple(out.shape)}")
+    lib = _lib.load()
+    nbytes = lib.selftok_lpips_distance_workspace_bytes(B, h * wd)
+    if nbytes == 0:
+        _lib.check(-1, "selftok_lpips_distance_workspace_bytes")
+    ws = lpips_workspace(feat.device, nbytes) if workspace is None else workspace
+    _lib.check(lib.selftok_lpips_distance(_p(feat), _p(w), _p(out), _p(ws), ws.numel() * ws.element_size(), B, h * wd, C, int(bool(accumulate)), _stream()),
+               "selftok_lpips_distance")
+    return out

@@ -6,7 +6,9 @@ README.md:89-94; see selftoktokenizer_amd/evaluate.py).  Sharded over ranks when
     python tools/eval_psnr.py --synthetic 16          # no checkpoint reachable: hash-generated weights / images / noise = the reference pipeline's golden run
 
 Prints ONE JSON line on rank 0: per-image and mean PSNR for the 50-step `decoding` and, when a renderer checkpoint is given, `decoding_with_renderer`;
-with --ssim also `ssim_mean` / `ssim_each` (the SSIM column of the reference's results table), computed on the GPU together with the PSNR."""
+with --ssim also `ssim_mean` / `ssim_each` (the SSIM column of the reference's results table), computed on the GPU together with the PSNR;
+with --lpips-backbone FILE --lpips-linear FILE (torchvision's AlexNet state dict and the lpips package's v0.1 alex.pth) also `lpips_mean` / `lpips_each`
+(selftoktokenizer_amd/lpips.py).  `--lpips` alone is accepted with --synthetic only: the hash-generated LPIPS network, labelled "synthetic" in the line."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -31,6 +33,9 @@ ap.add_argument("--gemm", default=None, choices=["fp32", "f16x2", "exact", "f16"
 ap.add_argument("--device-io", action="store_true", help="resize / crop / normalise the decoded files on the GPU (preprocess.DeviceLoader): the same values, bit for bit")
 ap.add_argument("--ssim", action="store_true", help="also the SSIM of every image (11 x 11 Gaussian window, sigma 1.5, valid region); both figures then come from one device call per batch")
 ap.add_argument("--metrics-u8", action="store_true", help="with --ssim: take PSNR and SSIM on the uint8 bytes save_image would write instead of the float tensors")
+ap.add_argument("--lpips-backbone", default=None, help="torchvision AlexNet state dict (features.{0,3,6,8,10}.{weight,bias}); with --lpips-linear: also LPIPS (alex, v0.1) of every image, on the GPU")
+ap.add_argument("--lpips-linear", default=None, help="the lpips package's v0.1 alex.pth (lin{0..4}.model.1.weight)")
+ap.add_argument("--lpips", action="store_true", help="with --synthetic and no weight files: LPIPS on the hash-generated network (values of the published definition on synthetic weights)")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file (rank 0)")
 a = ap.parse_args()
 
@@ -61,9 +66,19 @@ else:
         paths = paths[:a.limit]
     assert paths, f"no image files under {a.images}"
     n, load, noise, src = len(paths), E.folder_loader(paths, a.data_size, device=dev if a.device_io else None), None, f"{len(paths)} files under {a.images}"
-if a.metrics_u8 and not a.ssim:
-    ap.error("--metrics-u8 needs --ssim (the device metrics route)")
+if bool(a.lpips_backbone) != bool(a.lpips_linear):
+    ap.error("--lpips-backbone and --lpips-linear go together")
+if a.lpips and not a.lpips_backbone and not a.synthetic:
+    ap.error("--lpips without --lpips-backbone / --lpips-linear needs --synthetic: the published LPIPS weights are not shipped")
+lpips_net = None
+if a.lpips_backbone or a.lpips:
+    from selftoktokenizer_amd.lpips import LpipsNet
+    lpips_net = LpipsNet.from_files(a.lpips_backbone, a.lpips_linear, dev) if a.lpips_backbone else LpipsNet.synthetic(dev)
+if a.metrics_u8 and not (a.ssim or lpips_net):
+    ap.error("--metrics-u8 needs --ssim or LPIPS (the device metrics route)")
 mkw = dict(metrics=("psnr", "ssim"), metrics_u8=a.metrics_u8) if a.ssim else {}
+if lpips_net is not None:
+    mkw = dict(metrics=("psnr", "ssim", "lpips") if a.ssim else ("psnr", "lpips"), metrics_u8=a.metrics_u8, lpips=lpips_net)
 res = E.evaluate(pipe, load, n, batch=a.batch, decoders=decoders, noise_fn=noise, seed=a.seed, renderer_pipe=rpipe, verbose=True, **mkw)
 D.barrier()
 if rank == 0:
@@ -74,6 +89,9 @@ if rank == 0:
     if a.ssim:                                   # BASELINE.md rows 17-18; the reference's table does not say which decoder produced them
         line["paper_reference_ssim"] = {"512": 0.709, "1024": 0.805,
                                         "note": "assets/results_table.PNG (README.md:61-65): ImageNet-val 50k at 256 x 256, decoder and SSIM variant not stated; needs the published weights"}
+    if lpips_net is not None:                    # BASELINE.md rows 17-18; neither the decoder nor the LPIPS variant is stated (alex v0.1 is the package default)
+        line["lpips_weights"] = lpips_net.source
+        line["paper_reference_lpips"] = {"512": 0.084, "1024": 0.063, "note": "assets/results_table.PNG: needs the published tokenizer, AlexNet and LPIPS weights"}
     print(json.dumps(line), flush=True)
     if a.out:
         open(a.out, "w").write(json.dumps(line) + "\n")
