@@ -171,6 +171,40 @@ size_t selftok_lpips_distance_workspace_bytes(int B, int npix);
 int selftok_lpips_distance(const float* feat, const float* w, double* out, void* workspace, size_t workspace_bytes, int B, int npix, int C,
                            int accumulate, hipStream_t stream);
 
+/* ---- rFID stages (FID InceptionV3, pool3): convolution into a channel slice, 3 x 3 pools, input stage with resize, spatial mean,
+ *      fp64 statistics ----------------------------------------------------------------------------------------------
+ * The kernels of selftoktokenizer_amd/fid.py (FID_DEFINITION states the metric; csrc/fid.hip states the arithmetic and every summation
+ * order).  Activations are channels-last fp32.  An output MAP has rows of `ldo` floats; an entry writes the channels co_off ..
+ * co_off + C - 1 of every output pixel and leaves every other byte of the map alone (0 <= co_off, co_off + C <= ldo), so the branches
+ * of an Inception block write one concatenated map.  Every refusal is decided on the host before any launch and returns SELFTOK_EINVAL
+ * with a message; an output depends on its own image alone.
+ *
+ * selftok_fid_conv2d_f32: selftok_lpips_conv2d_f32 (the same kernel body, arithmetic and packed weight: selftok_lpips_conv2d_packed_floats)
+ *   with a padding per axis, 0 <= pad_h < KH and 0 <= pad_w < KW, and the slice.  ldo = Cout, co_off = 0, pad_h = pad_w gives the LPIPS
+ *   entry's bits.
+ * selftok_fid_pool3_f32: 3 x 3 windows.  mode 0: max, stride 2, no padding (floor; H, W >= 3); mode 1: max, stride 1, pad 1 (a padding
+ *   tap never takes part); mode 2: average, stride 1, pad 1, divisor = the number of in-image taps (count_include_pad=False): the taps
+ *   added from +0.0f in (kh, kw) order in fp32, then one division.  A NaN in a window is the window's result.
+ * selftok_fid_input: src [B, 3, H, W] (bf16 or fp32, NCHW) -> out [B, OH, OW, 3] in [-1, 1]: x = float32(v) * 2 - 1 of a [0, 1] image
+ *   (src_signed == 0), a signed image as it is; quantize != 0: byte / 255 * 2 - 1 of the byte selftok_lpips_input takes (an unsigned
+ *   image in its own type, a signed one from (v + 1) / 2 in fp32).  ytab / xtab (device, both or neither): 3 * OH (3 * OW) ints, i0[],
+ *   i1[] and the bits of the fp32 lambda[] of every output row (column); the converted values are blended in fp32, each operation rounded
+ *   on its own, top = a + lx * (b - a), bot = c + lx * (d - c), x = top + ly * (bot - top).  Indices are clamped into the image.
+ *   Without tables OH x OW must be H x W and the converted values are stored as they are.
+ * selftok_fid_spatial_mean_f32: in [N, npix, C] -> out [N, C]: the pixels added from +0.0f in index order in fp32, then / (float)npix.
+ * selftok_fid_stats: x [N, D] fp32 -> mu [D] and sigma [D, D] fp64 (device), sigma the unbiased covariance (1 / (N - 1)), two passes
+ *   in fp64 in the fixed order csrc/fid.hip states (chunks of 256 rows ascending, a fixed pairwise tree across chunks), no atomics;
+ *   sigma is exactly symmetric.  2 <= N <= 256 * 65535, D % 16 == 0.  Workspace (one fp64 per chunk and column) from the query; 0 with
+ *   the error set when N or D is refused. */
+int selftok_fid_conv2d_f32(const float* in, const float* packed, const float* bias, float* out, int N, int H, int W, int Cin, int Cout,
+                           int KH, int KW, int stride, int pad_h, int pad_w, int ldo, int co_off, int relu, hipStream_t stream);
+int selftok_fid_pool3_f32(const float* in, float* out, int N, int H, int W, int C, int mode, int ldo, int co_off, hipStream_t stream);
+int selftok_fid_input(const void* src, int src_bf16, int src_signed, int quantize, float* out, int B, int H, int W, int OH, int OW,
+                      const int* ytab, const int* xtab, hipStream_t stream);
+int selftok_fid_spatial_mean_f32(const float* in, float* out, int N, int npix, int C, hipStream_t stream);
+size_t selftok_fid_stats_workspace_bytes(int N, int D);
+int selftok_fid_stats(const float* x, double* mu, double* sigma, void* workspace, size_t workspace_bytes, int N, int D, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,12 @@ EXT_SIGNATURES = {
     "selftok_lpips_input": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "selftok_lpips_distance_workspace_bytes": (_sz, [_i, _i]),
     "selftok_lpips_distance": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "selftok_fid_conv2d_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp]),
+    "selftok_fid_pool3_f32": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
+    "selftok_fid_input": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "selftok_fid_spatial_mean_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "selftok_fid_stats_workspace_bytes": (_sz, [_i, _i]),
+    "selftok_fid_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
 }
 
 

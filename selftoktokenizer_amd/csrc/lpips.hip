@@ -25,6 +25,8 @@
 // ascending, a butterfly adds the 64 lanes; a wave adds its 16 pixels of a 64-pixel tile in ascending order, the four waves are added
 // as (w0 + w1) + (w2 + w3); the finish adds a pair's tiles in index order and divides by the pixel count.  No atomics.
 #include "common.h"
+#include "conv_f32_shared.h"
+#include "u8_shared.h"
 #include "selftok_hip_ext.h"
 #include <stdio.h>
 
@@ -33,119 +35,14 @@
 namespace selftok {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 64, BN = 64, KT = 16, LDS_STRIDE = 68, NT = 256;
+using conv_f32::BM; using conv_f32::BN; using conv_f32::KT; using conv_f32::NT; using conv_f32::ConvArgs; using conv_f32::out_side;
 constexpr int MIN_SIDE = 31;
 
-struct ConvArgs {
-    const float* in; const float* wp; const float* bias; float* out;
-    int H, W, Cin, OH, OW, Cout, CoutP, KH, KW, stride, pad, K, KP, relu;
-    long M;
-};
-
-// the tap walk of one gather lane: k -> (kh, kw, ci), advanced without a division
-struct Tap {
-    int kh, kw, ci;
-    __device__ __forceinline__ void advance(int by, int Cin, int KW)
-    {
-        ci += by;
-        while (ci >= Cin) { ci -= Cin; if (++kw == KW) { kw = 0; ++kh; } }
-    }
-};
-
+// the convolution of record: conv_f32_shared.h's tile body (__builtin_amdgcn_mfma_f32_32x32x2f32), shared with csrc/fid.hip
 template <bool VEC>
 __global__ void __launch_bounds__(NT) lpips_conv_kernel(ConvArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float As[KT * LDS_STRIDE];
-    __shared__ __attribute__((aligned(16))) float Bs[KT * LDS_STRIDE];   // written as float4: bk * 68 + bc is a multiple of 4
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long m0 = (long)blockIdx.x * BM;
-    const int n0 = blockIdx.y * BN;
-
-    // gather role: row ar of the tile, taps akq .. akq + 3 of every step
-    const int ar = tid >> 2, akq = (tid & 3) * 4;
-    const long am = m0 + ar;
-    const bool arow = am < a.M;
-    int iy0 = 0, ix0 = 0;
-    const float* aimg = a.in;
-    if (arow) {
-        const long per = (long)a.OH * a.OW;
-        const long n = am / per;
-        const int rem = (int)(am - n * per);
-        const int oy = rem / a.OW, ox = rem - oy * a.OW;
-        iy0 = oy * a.stride - a.pad; ix0 = ox * a.stride - a.pad;
-        aimg = a.in + (size_t)n * a.H * a.W * a.Cin;
-    }
-    Tap tap{0, 0, 0};
-    tap.advance(akq, a.Cin, a.KW);
-    // weight role: row bk of the step, columns bc .. bc + 3
-    const int bk = tid >> 4, bc = (tid & 15) * 4;
-    const float* bsrc = a.wp + (size_t)bk * a.CoutP + n0 + bc;
-
-    float4 areg, breg;
-    auto fetch = [&](int k0) {
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (VEC) {
-            if (arow && k0 + akq < a.K) {
-                const int iy = iy0 + tap.kh, ix = ix0 + tap.kw;
-                if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
-                    const float4 q = *(const float4*)(aimg + ((size_t)iy * a.W + ix) * a.Cin + tap.ci);
-                    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-                }
-            }
-        } else {
-            Tap t = tap;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (arow && k0 + akq + j < a.K) {
-                    const int iy = iy0 + t.kh, ix = ix0 + t.kw;
-                    if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v[j] = aimg[((size_t)iy * a.W + ix) * a.Cin + t.ci];
-                }
-                t.advance(1, a.Cin, a.KW);
-            }
-        }
-        areg = make_float4(v[0], v[1], v[2], v[3]);
-        breg = *(const float4*)(bsrc + (size_t)k0 * a.CoutP);
-        tap.advance(KT, a.Cin, a.KW);
-    };
-
-    f32x16 acc[KT / 2];                                           // chain j = acc[j]
-#pragma unroll
-    for (int j = 0; j < KT / 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[j][i] = 0.0f;
-    const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
-    const int fr = lane & 31, fk = lane >> 5;
-
-    fetch(0);
-    for (int k0 = 0; k0 < a.KP; k0 += KT) {
-        __syncthreads();                                          // the previous step's MFMA reads are done
-        As[(akq + 0) * LDS_STRIDE + ar] = areg.x; As[(akq + 1) * LDS_STRIDE + ar] = areg.y;
-        As[(akq + 2) * LDS_STRIDE + ar] = areg.z; As[(akq + 3) * LDS_STRIDE + ar] = areg.w;
-        *(float4*)(Bs + bk * LDS_STRIDE + bc) = breg;
-        __syncthreads();
-        if (k0 + KT < a.KP) fetch(k0 + KT);                       // in flight while the MFMAs below run
-#pragma unroll
-        for (int kk = 0; kk < KT; kk += 2) {                      // taps kk, kk + 1 of this step -> chain kk / 2
-            const float av = As[(kk + fk) * LDS_STRIDE + wm + fr];
-            const float bv = Bs[(kk + fk) * LDS_STRIDE + wn + fr];
-            acc[kk / 2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[kk / 2], 0, 0, 0);
-        }
-    }
-    const f32x16 sum = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-
-    const int co = n0 + wn + fr;
-    if (co >= a.Cout) return;
-    const float bias = a.bias ? a.bias[co] : 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const long m = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * fk;
-        if (m >= a.M) continue;
-        float v = a.bias ? sum[r] + bias : sum[r];
-        if (a.relu) v = v < 0.0f ? 0.0f : v;
-        a.out[(size_t)m * a.Cout + co] = v;
-    }
+    conv_f32::conv_tile<VEC>(a);
 }
 
 // channels-last 3 x 3 stride 2 max-pool, floor mode, no padding: every window lies inside the image.  A NaN wins (torch's rule).
@@ -168,27 +65,6 @@ __global__ void __launch_bounds__(NT) lpips_pool_kernel(const float* __restrict_
             if (v > m || v != v) m = v;
         }
     out[i] = m;
-}
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ float round_bf16(float f)              // fp32 -> nearest bf16 (ties to even), as fp32; not for NaN
-{
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return __uint_as_float(u & 0xFFFF0000u);
-}
-
-// csrc/image_io.hip's to_u8_one, copied (as csrc/image_metrics.hip does): pinned to tests/image_io_cases.py::to_u8_bf16 / to_u8_f32
-template <bool BF16>
-__device__ __forceinline__ unsigned char to_u8_one(float x)
-{
-    if (x != x) return 0;
-    float y = x * 255.0f;
-    if (BF16) y = round_bf16(y);
-    y = y + 0.5f;
-    if (BF16) y = round_bf16(y);
-    y = y < 0.0f ? 0.0f : (y > 255.0f ? 255.0f : y);
-    return (unsigned char)(int)y;
 }
 
 struct InputArgs {
@@ -281,9 +157,6 @@ __global__ void __launch_bounds__(64) lpips_dist_finish_kernel(const double* __r
 
 bool fail(const char* msg) { set_last_error(msg); return false; }
 
-// output side of a convolution / pool, 0 when there is no output pixel
-int out_side(int in, int k, int stride, int pad) { const long s = (long)in + 2l * pad - k; return s < 0 ? 0 : (int)(s / stride + 1); }
-
 bool conv_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int* OH, int* OW)
 {
     char msg[256];
@@ -332,8 +205,8 @@ int selftok_lpips_conv2d_f32(const float* in, const float* packed, const float* 
     if (((uintptr_t)in & 15) != 0 || ((uintptr_t)packed & 15) != 0 || ((uintptr_t)out & 3) != 0 || ((uintptr_t)bias & 3) != 0) {
         set_last_error("lpips_conv2d: in and packed must be 16-byte aligned, out and bias 4-byte aligned"); return SELFTOK_EINVAL;
     }
-    ConvArgs a{in, packed, bias, out, H, W, Cin, OH, OW, Cout, (Cout + BN - 1) / BN * BN, KH, KW, stride, pad, KH * KW * Cin,
-               (KH * KW * Cin + KT - 1) / KT * KT, relu != 0, (long)N * OH * OW};
+    ConvArgs a{in, packed, bias, out, H, W, Cin, OH, OW, Cout, (Cout + BN - 1) / BN * BN, KH, KW, stride, pad, pad, KH * KW * Cin,
+               (KH * KW * Cin + KT - 1) / KT * KT, relu != 0, Cout, 0, (long)N * OH * OW};
     const dim3 grid((unsigned)((a.M + BM - 1) / BM), (unsigned)(a.CoutP / BN));
     if (grid.y > 65535u) { set_last_error("lpips_conv2d: Cout above 64 * 65535"); return SELFTOK_EINVAL; }
     if (Cin % 4 == 0) hipLaunchKernelGGL(lpips_conv_kernel<true>, grid, dim3(NT), 0, stream, a);

@@ -65,7 +65,7 @@ def metrics_each(recon: torch.Tensor, original: torch.Tensor, quantize: bool = F
 
 def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int, batch: int = 64, decoders: Sequence[str] = ("diffusion",),
              noise_fn: Optional[Callable[[int, int], torch.Tensor]] = None, seed: Optional[int] = 1234, renderer_pipe=None, verbose: bool = False,
-             metrics: Sequence[str] = ("psnr",), metrics_u8: bool = False, lpips=None) -> Dict:
+             metrics: Sequence[str] = ("psnr",), metrics_u8: bool = False, lpips=None, fid=None) -> Dict:
     """PSNR of `n_images` images through `pipe` (and `renderer_pipe` for the one-step decoder), this rank's contiguous shard of them
     (dist.shard_range) in batches of `batch`; per-image values are gathered to every rank (one all_gather_into_tensor per decoder at the end).
     load_batch(lo, hi) -> float tensor [hi-lo, 3, H, W] in [-1, 1] (host or device).  noise_fn(lo, hi) -> [hi-lo, 16, h, w] replaces the
@@ -74,12 +74,20 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     copy of the images, one read of the [n, 2] results at the end): every decoder's dict gains `ssim_mean` / `ssim_each` and the result says which SSIM it is
     (`metric_definition`).  metrics_u8: take both on the bytes `save_image` would write (needs "ssim": the host route has no such mode).
     "lpips" with `lpips=` an lpips.LpipsNet (the weights are not shipped, so there is no default network): the device route as for "ssim", every decoder's dict
-    also gains `lpips_mean` / `lpips_each` and `metric_definition["lpips"]` states the definition and where the weights came from; metrics_u8 applies to it too."""
+    also gains `lpips_mean` / `lpips_each` and `metric_definition["lpips"]` states the definition and where the weights came from; metrics_u8 applies to it too.
+    "rfid" with `fid=` a fid.InceptionNet (no default network either): the device route; the pool3 features of the originals (once) and of every decoder's
+    reconstructions are collected per batch and gathered like the per-image values, and the statistics are taken of the GATHERED matrices, so the figure does
+    not depend on the sharding.  Every decoder's dict gains `rfid`, `rfid_n` and `rfid_rank_deficient` (fewer than 2049 images: the covariances are singular
+    and the figure is only comparable at the same N); `metric_definition["rfid"]` states the definition and the weights' source; metrics_u8 applies."""
     with_lpips = "lpips" in metrics and lpips is not None
-    bad = [m for m in metrics if m not in ("psnr", "ssim") and not (m == "lpips" and with_lpips)]
+    with_fid = "rfid" in metrics and fid is not None
+    bad = [m for m in metrics if m not in ("psnr", "ssim") and not (m == "lpips" and with_lpips) and not (m == "rfid" and with_fid)]
     if bad or not metrics:
-        raise ValueError(f"metrics {tuple(metrics)!r}: expected a non-empty subset of ('psnr', 'ssim')" + (", or 'lpips' together with lpips=<LpipsNet>" if "lpips" in bad else ""))
-    on_device = "ssim" in metrics or with_lpips
+        raise ValueError(f"metrics {tuple(metrics)!r}: expected a non-empty subset of ('psnr', 'ssim')" + (", or 'lpips' together with lpips=<LpipsNet>" if "lpips" in bad else "")
+                         + (", or 'rfid' together with fid=<InceptionNet>" if "rfid" in bad else ""))
+    if with_fid and n_images < 2:
+        raise ValueError(f"'rfid' needs at least 2 images (a covariance), got {n_images}")
+    on_device = "ssim" in metrics or with_lpips or with_fid
     if metrics_u8 and not on_device:
         raise ValueError("metrics_u8 needs 'ssim' in `metrics` (the device route); the host PSNR route is the float one")
     world, rank = D.world_size(), D.rank()       # the dist module's view: sharding and the gather below must agree (ADVICE r5)
@@ -88,6 +96,8 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     if seed is not None:
         torch.manual_seed(int(seed) + rank)
     vals = {d: [] for d in decoders}
+    feats = {d: [] for d in decoders}            # "rfid": pool3 features [b, 2048] fp32 per batch, the originals under None
+    feats[None] = []
     ids_all = []
     for b0 in range(lo, hi, batch):
         b1 = min(b0 + batch, hi)
@@ -95,6 +105,8 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
         tokens = pipe.encoding(imgs, device=pipe.device)
         ids = tokens.detach().cpu().numpy()                       # the reference round-trips the ids through a host .npy (test.py:38-39)
         ids_all.append(ids)
+        if with_fid:
+            feats[None].append(fid.pool3(imgs, signed=True, quantize=metrics_u8))
         for d in decoders:
             if d == "diffusion":
                 kw = {} if noise_fn is None else {"noise": noise_fn(b0, b1)}
@@ -109,12 +121,18 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
                 if with_lpips:
                     m = torch.cat([m, lpips(rec.detach(), imgs, original_signed=True, quantize=metrics_u8)[:, None]], dim=1)      # [b, 3]
                 vals[d].append(m)
+                if with_fid:
+                    feats[d].append(fid.pool3(rec.detach(), signed=False, quantize=metrics_u8))
             else:
                 vals[d].append(psnr_each(rec, imgs))
         if verbose and rank == 0:
             so_far = (lambda d: float(psnr_of_mse(torch.cat(vals[d])[:, 1].cpu().numpy()).mean())) if on_device else (lambda d: np.concatenate(vals[d]).mean())
             print(f"[eval] images {b0}..{b1 - 1} of shard {lo}..{hi - 1}: " + ", ".join(f"{d} {so_far(d):.4f} dB so far" for d in decoders), flush=True)
     out = {"images": int(n_images), "ranks": world, "batch": int(batch), "shard": [int(lo), int(hi)]}
+    if with_fid:
+        from . import fid as FD
+        gathered = lambda key: D.all_gather_rows(torch.cat(feats[key]) if feats[key] else torch.zeros(0, FD.FEATURES, dtype=torch.float32, device=pipe.device), counts)
+        mu0, sigma0 = (t.cpu().numpy() for t in FD.statistics(gathered(None)))
     for d in decoders:
         if on_device:
             mine = torch.cat(vals[d]) if vals[d] else torch.zeros(0, 3 if with_lpips else 2, dtype=torch.float64, device=pipe.device)
@@ -124,6 +142,8 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
                       "ssim_mean": float(ssim.mean()) if ssim.size else float("nan"), "ssim_each": [round(float(v), 9) for v in ssim]}
             if with_lpips:
                 out[d].update({"lpips_mean": float(allv[:, 2].mean()) if ssim.size else float("nan"), "lpips_each": [round(float(v), 9) for v in allv[:, 2]]})
+            if with_fid:
+                out[d].update({"rfid": FD.frechet_distance(*FD.statistics(gathered(d)), mu0, sigma0), "rfid_n": int(n_images), "rfid_rank_deficient": n_images <= FD.FEATURES})
             continue
         mine = torch.from_numpy(np.concatenate(vals[d]) if vals[d] else np.zeros(0)).to(torch.float64)
         allv = D.all_gather_rows(mine.to(pipe.device), counts).cpu().numpy()      # returns `mine` when there is no exchange to perform
@@ -133,6 +153,8 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
         if with_lpips:
             from .lpips import LPIPS_DEFINITION
             out["metric_definition"]["lpips"] = dict(LPIPS_DEFINITION, weights=lpips.source)
+        if with_fid:
+            out["metric_definition"]["rfid"] = dict(FD.FID_DEFINITION, weights=fid.source, resized=bool(fid.resize))
     out["token_ids_first_image"] = ids_all[0][0, :8].tolist() if ids_all else []
     return out
 

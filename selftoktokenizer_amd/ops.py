@@ -1278,3 +1278,114 @@ def lpips_distance(feat: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tens
     _lib.check(lib.selftok_lpips_distance(_p(feat), _p(w), _p(out), _p(ws), ws.numel() * ws.element_size(), B, h * wd, C, int(bool(accumulate)), _stream()),
                "selftok_lpips_distance")
     return out
+
+
+# ---- rFID stages (csrc/fid.hip, include/selftok_hip_ext.h): channels-last fp32 activations; an output may be a channel slice of a wider map ----
+FID_POOL_MODES = {"max_s2": 0, "max_s1p1": 1, "avg_s1p1": 2}
+
+
+def _fid_slice_out(what: str, out: Optional[torch.Tensor], shape, C: int, co_off: int, device):
+    """the output map of a slice-writing entry: `out` [N, OH, OW, ldo] (contiguous fp32, ldo >= co_off + C) or a fresh [N, OH, OW, C] when None"""
+    N, OH, OW = shape
+    if out is None:
+        if co_off:
+            raise _lib.SelftokHipError(f"{what}: a channel offset needs the `out` map it points into")
+        return torch.empty(N, max(OH, 0), max(OW, 0), C, dtype=torch.float32, device=device)
+    if out.dtype != torch.float32 or out.dim() != 4 or tuple(out.shape[:3]) != (N, OH, OW) or not out.is_contiguous() or co_off < 0 or out.shape[3] < co_off + C:
+        raise _lib.SelftokHipError(f"{what}: `out` must be a contiguous float32 [{N}, {OH}, {OW}, ldo >= {co_off} + {C}], got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def fid_conv2d(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], Cout: int, KH: int, KW: int, stride: int, pad_h: int, pad_w: int, relu: bool = True,
+               out: Optional[torch.Tensor] = None, co_off: int = 0) -> torch.Tensor:
+    """lpips_conv2d's convolution (same kernel body, same packed weight) with a padding per axis, writing channels co_off .. co_off + Cout - 1 of the map
+    `out` [N, OH, OW, ldo] and nothing else of it.  Returns the map."""
+    _need_cuda(x, packed, bias, out)
+    x, packed = _lpips_f32("x", x, 4), _lpips_f32("packed", packed, 2)
+    bias = None if bias is None else _lpips_f32("bias", bias, 1)
+    N, H, W, Cin = x.shape
+    lib = _lib.load()
+    if packed.numel() != lib.selftok_lpips_conv2d_packed_floats(Cin, Cout, KH, KW) or (bias is not None and bias.numel() != Cout):
+        raise _lib.SelftokHipError(f"fid_conv2d: packed weight of {packed.numel()} floats / bias do not belong to Cin {Cin}, Cout {Cout}, {KH} x {KW}")
+    OH, OW = (H + 2 * pad_h - KH) // stride + 1, (W + 2 * pad_w - KW) // stride + 1
+    if H + 2 * pad_h < KH or W + 2 * pad_w < KW:                  # decided here: an empty tensor has no pointer to hand to the entry
+        raise _lib.SelftokHipError(f"fid_conv2d: {H} x {W} input has no output pixel under a {KH} x {KW} kernel with pad {pad_h}, {pad_w}")
+    out = _fid_slice_out("fid_conv2d", out, (N, OH, OW), Cout, co_off, x.device)
+    _lib.check(lib.selftok_fid_conv2d_f32(_p(x), _p(packed), _p(bias), _p(out), N, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w, out.shape[3], co_off,
+                                          int(bool(relu)), _stream()), "selftok_fid_conv2d_f32")
+    return out
+
+
+def fid_pool3(x: torch.Tensor, mode: str, out: Optional[torch.Tensor] = None, co_off: int = 0) -> torch.Tensor:
+    """3 x 3 pool of x [N, H, W, C]: mode "max_s2" (stride 2, no padding), "max_s1p1" or "avg_s1p1" (stride 1, pad 1; the average divides by the number of
+    in-image taps), into channels co_off .. co_off + C - 1 of the map `out`.  Returns the map."""
+    _need_cuda(x, out)
+    x = _lpips_f32("x", x, 4)
+    if mode not in FID_POOL_MODES:
+        raise _lib.SelftokHipError(f"fid_pool3: mode {mode!r}: expected one of {sorted(FID_POOL_MODES)}")
+    N, H, W, C = x.shape
+    if mode == "max_s2" and min(H, W) < 3:
+        raise _lib.SelftokHipError(f"fid_pool3: max_s2 needs H, W >= 3 (one window), got {H} x {W}")
+    PH, PW = ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == "max_s2" else (H, W)
+    out = _fid_slice_out("fid_pool3", out, (N, PH, PW), C, co_off, x.device)
+    _lib.check(_lib.load().selftok_fid_pool3_f32(_p(x), _p(out), N, H, W, C, FID_POOL_MODES[mode], out.shape[3], co_off, _stream()), "selftok_fid_pool3_f32")
+    return out
+
+
+def fid_input(images: torch.Tensor, signed: bool, quantize: bool = False, tables=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """images [B, 3, H, W] (bf16 or fp32; in [-1, 1] when `signed`, else in [0, 1]) -> [B, OH, OW, 3] fp32 in [-1, 1].  `tables`: (ytab, xtab) int32 device
+    tensors [3, OH] and [3, OW] from fid.resize_tables (i0, i1, the bits of the fp32 lambda): the bilinear resize; None: the image as it is."""
+    if images.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.SelftokHipError(f"fid_input: dtype {images.dtype}: expected bfloat16 or float32")
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise _lib.SelftokHipError(f"fid_input: expected a [B, 3, H, W] tensor, got {tuple(images.shape)}")
+    _need_cuda(images, out)
+    images = images.contiguous()
+    B, _, H, W = images.shape
+    OH, OW, ytab, xtab = H, W, None, None
+    if tables is not None:
+        ytab, xtab = tables
+        _need_cuda(ytab, xtab)
+        for t in (ytab, xtab):
+            if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != 3 or not t.is_contiguous():
+                raise _lib.SelftokHipError(f"fid_input: a tap table must be a contiguous int32 [3, n], got {t.dtype} {tuple(t.shape)}")
+        OH, OW = ytab.shape[1], xtab.shape[1]
+    if out is None:
+        out = torch.empty(B, OH, OW, 3, dtype=torch.float32, device=images.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, OH, OW, 3) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"fid_input: `out` must be a contiguous float32 {(B, OH, OW, 3)}, got {out.dtype} {tuple(out.shape)}")
+    _lib.check(_lib.load().selftok_fid_input(_p(images), int(images.dtype == torch.bfloat16), int(bool(signed)), int(bool(quantize)), _p(out), B, H, W, OH, OW,
+                                             _p(ytab), _p(xtab), _stream()), "selftok_fid_input")
+    return out
+
+
+def fid_spatial_mean(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [N, h, w, C] fp32 channels-last -> [N, C]: per image and channel the pixels added in index order in fp32, then one division"""
+    _need_cuda(x, out)
+    x = _lpips_f32("x", x, 4)
+    N, h, w, C = x.shape
+    if out is None:
+        out = torch.empty(N, C, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (N, C) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"fid_spatial_mean: `out` must be a contiguous float32 {(N, C)}, got {out.dtype} {tuple(out.shape)}")
+    _lib.check(_lib.load().selftok_fid_spatial_mean_f32(_p(x), _p(out), N, h * w, C, _stream()), "selftok_fid_spatial_mean_f32")
+    return out
+
+
+def fid_stats(x: torch.Tensor, mu: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """x [N, D] fp32 -> (mu [D], sigma [D, D]) fp64 on the device: the mean and the unbiased covariance, two fp64 passes in the fixed order csrc/fid.hip states"""
+    _need_cuda(x, mu, sigma, workspace)
+    x = _lpips_f32("x", x, 2)
+    N, D = x.shape
+    lib = _lib.load()
+    nbytes = lib.selftok_fid_stats_workspace_bytes(N, D)
+    if nbytes == 0:
+        _lib.check(-1, "selftok_fid_stats_workspace_bytes")
+    for name, t, shape in (("mu", mu, (D,)), ("sigma", sigma, (D, D))):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise _lib.SelftokHipError(f"fid_stats: `{name}` must be a contiguous float64 {shape}, got {t.dtype} {tuple(t.shape)}")
+    mu = torch.empty(D, dtype=torch.float64, device=x.device) if mu is None else mu
+    sigma = torch.empty(D, D, dtype=torch.float64, device=x.device) if sigma is None else sigma
+    ws = lpips_workspace(x.device, nbytes) if workspace is None else workspace
+    _lib.check(lib.selftok_fid_stats(_p(x), _p(mu), _p(sigma), _p(ws), ws.numel() * ws.element_size(), N, D, _stream()), "selftok_fid_stats")
+    return mu, sigma

@@ -8,7 +8,9 @@ README.md:89-94; see selftoktokenizer_amd/evaluate.py).  Sharded over ranks when
 Prints ONE JSON line on rank 0: per-image and mean PSNR for the 50-step `decoding` and, when a renderer checkpoint is given, `decoding_with_renderer`;
 with --ssim also `ssim_mean` / `ssim_each` (the SSIM column of the reference's results table), computed on the GPU together with the PSNR;
 with --lpips-backbone FILE --lpips-linear FILE (torchvision's AlexNet state dict and the lpips package's v0.1 alex.pth) also `lpips_mean` / `lpips_each`
-(selftoktokenizer_amd/lpips.py).  `--lpips` alone is accepted with --synthetic only: the hash-generated LPIPS network, labelled "synthetic" in the line."""
+(selftoktokenizer_amd/lpips.py).  `--lpips` alone is accepted with --synthetic only: the hash-generated LPIPS network, labelled "synthetic" in the line;
+with --fid-weights FILE (pytorch-fid's pt_inception-2015-12-05 state dict) also `rfid` per decoder (selftoktokenizer_amd/fid.py: InceptionV3 pool3 features
+and the fp64 statistics on the GPU, the Frechet distance on the host); `--fid` alone, like `--lpips`, with --synthetic only."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -36,6 +38,8 @@ ap.add_argument("--metrics-u8", action="store_true", help="with --ssim: take PSN
 ap.add_argument("--lpips-backbone", default=None, help="torchvision AlexNet state dict (features.{0,3,6,8,10}.{weight,bias}); with --lpips-linear: also LPIPS (alex, v0.1) of every image, on the GPU")
 ap.add_argument("--lpips-linear", default=None, help="the lpips package's v0.1 alex.pth (lin{0..4}.model.1.weight)")
 ap.add_argument("--lpips", action="store_true", help="with --synthetic and no weight files: LPIPS on the hash-generated network (values of the published definition on synthetic weights)")
+ap.add_argument("--fid-weights", default=None, help="pytorch-fid's pt_inception-2015-12-05 state dict: also rFID (InceptionV3 pool3) of every decoder's reconstructions against the originals")
+ap.add_argument("--fid", action="store_true", help="with --synthetic and no weight file: rFID on the hash-generated InceptionV3 (the published definition on synthetic weights)")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file (rank 0)")
 a = ap.parse_args()
 
@@ -74,11 +78,19 @@ lpips_net = None
 if a.lpips_backbone or a.lpips:
     from selftoktokenizer_amd.lpips import LpipsNet
     lpips_net = LpipsNet.from_files(a.lpips_backbone, a.lpips_linear, dev) if a.lpips_backbone else LpipsNet.synthetic(dev)
-if a.metrics_u8 and not (a.ssim or lpips_net):
-    ap.error("--metrics-u8 needs --ssim or LPIPS (the device metrics route)")
+if a.fid and not a.fid_weights and not a.synthetic:
+    ap.error("--fid without --fid-weights needs --synthetic: the published InceptionV3 weights are not shipped")
+fid_net = None
+if a.fid_weights or a.fid:
+    from selftoktokenizer_amd.fid import InceptionNet
+    fid_net = InceptionNet.from_files(a.fid_weights, dev) if a.fid_weights else InceptionNet.synthetic(dev)
+if a.metrics_u8 and not (a.ssim or lpips_net or fid_net):
+    ap.error("--metrics-u8 needs --ssim, LPIPS or rFID (the device metrics route)")
 mkw = dict(metrics=("psnr", "ssim"), metrics_u8=a.metrics_u8) if a.ssim else {}
 if lpips_net is not None:
     mkw = dict(metrics=("psnr", "ssim", "lpips") if a.ssim else ("psnr", "lpips"), metrics_u8=a.metrics_u8, lpips=lpips_net)
+if fid_net is not None:
+    mkw = dict(mkw, metrics=tuple(mkw.get("metrics", ("psnr",))) + ("rfid",), metrics_u8=a.metrics_u8, fid=fid_net)
 res = E.evaluate(pipe, load, n, batch=a.batch, decoders=decoders, noise_fn=noise, seed=a.seed, renderer_pipe=rpipe, verbose=True, **mkw)
 D.barrier()
 if rank == 0:
@@ -92,6 +104,9 @@ if rank == 0:
     if lpips_net is not None:                    # BASELINE.md rows 17-18; neither the decoder nor the LPIPS variant is stated (alex v0.1 is the package default)
         line["lpips_weights"] = lpips_net.source
         line["paper_reference_lpips"] = {"512": 0.084, "1024": 0.063, "note": "assets/results_table.PNG: needs the published tokenizer, AlexNet and LPIPS weights"}
+    if fid_net is not None:                      # the variant the paper used is not stated; rFID depends on N below 2049 images (rfid_rank_deficient)
+        line["fid_weights"] = fid_net.source
+        line["paper_reference_rfid"] = {"note": "assets/results_table.PNG: ImageNet-val 50k at 256 x 256; needs the published tokenizer and InceptionV3 weights"}
     print(json.dumps(line), flush=True)
     if a.out:
         open(a.out, "w").write(json.dumps(line) + "\n")
