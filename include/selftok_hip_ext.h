@@ -114,12 +114,27 @@ int selftok_vq_topk_packed_f32(const float* z, const float* packed, void* ids, f
  * (out = NULL).  The residual entry computes resid + gate * (A W^T + bias) as selftok_linear_f16x2_split_residual does (gate NULL,
  * per-sample or per-token table).  overflow bit 0 is OR-ed for a non-finite output (an |activation| >= 65504 is one).
  * Refusals as the f16x2 entries: N % 128, K % 32, null / unaligned pointers, bad strides -> SELFTOK_EINVAL; M == 0 returns 0 without
- * a launch.  There is no split-K variant: small row counts belong on selftok_linear_f16x2_split_k. */
+ * a launch.  These two entries walk all of K in one work-group per output tile; small row counts (one to four images) belong on
+ * selftok_linear_f16x2_split_k, or -- staying in this lossy arithmetic -- on the split-K variants below. */
 int selftok_linear_f16_split(const void* a_blk, const void* packed, const float* bias, float* out, void* out_blk, long ldo,
                              int M, int N, int K, int flags, int* overflow, hipStream_t stream);
 int selftok_linear_f16_split_residual(const void* a_blk, const void* packed, const float* bias,
                                       const float* resid, long ldr, const float* gate, long gate_stride_b, long gate_stride_t, int T,
                                       float* out, long ldo, int M, int N, int K, int* overflow, hipStream_t stream);
+
+/* Split-K variants of the two entries above (csrc/gemm_f16_splitk.hip), with the argument lists of selftok_linear_f16x2_split_k /
+ * selftok_linear_f16x2_split_residual_k: `ksplit` work-groups share an output tile, each over K / 32 / ksplit consecutive k-tiles in
+ * ascending 16-deep steps, and write raw fp32 partial sums to plane s of `workspace` ([ksplit][M][N] fp32, 16-byte aligned,
+ * its size in bytes is what selftok_linear_f16x2_splitk_workspace_bytes returns; nothing beyond is touched); the second launch is the f16x2 route's
+ * reduction: planes added in ascending order, then bias and the epilogue.  Deterministic.  LOSSY as above; on operands exactly
+ * representable in fp16 the results equal those of the f16x2 _k entries with the same ksplit, bit for bit.  ksplit == 1 forwards to
+ * the single-pass entry (workspace not read).  Refused (SELFTOK_EINVAL) on top of the refusals above, exactly as the f16x2 _k entries
+ * refuse: ksplit < 1 or > 64, ksplit not a divisor of K / 32, workspace NULL or not 16-byte aligned. */
+int selftok_linear_f16_split_k(const void* a_blk, const void* packed, const float* bias, float* out, void* out_blk, long ldo,
+                               int M, int N, int K, int flags, int ksplit, void* workspace, int* overflow, hipStream_t stream);
+int selftok_linear_f16_split_residual_k(const void* a_blk, const void* packed, const float* bias,
+                                        const float* resid, long ldr, const float* gate, long gate_stride_b, long gate_stride_t, int T,
+                                        float* out, long ldo, int M, int N, int K, int ksplit, void* workspace, int* overflow, hipStream_t stream);
 
 /* ---- single-pass fp16 joint attention (the attention of the "f16" mode) ---------------------------------
  * selftok_attn_f32 / selftok_attn_kmask_f32 with ONE fp16 matrix instruction per product -- LOSSY (11 significand bits per

@@ -95,6 +95,8 @@ EXT_SIGNATURES = {
     "selftok_vq_topk_packed_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "selftok_linear_f16_split": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _vp]),
     "selftok_linear_f16_split_residual": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _l, _l, _i, _vp, _l, _i, _i, _i, _vp, _vp]),
+    "selftok_linear_f16_split_k": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "selftok_linear_f16_split_residual_k": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _l, _l, _i, _vp, _l, _i, _i, _i, _i, _vp, _vp, _vp]),
     "selftok_attn_f16": (_i, [_vp, _vp, _l, _vp]),
     "selftok_lpips_conv2d_packed_floats": (_sz, [_i, _i, _i, _i]),
     "selftok_lpips_conv2d_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp]),

@@ -26,8 +26,8 @@
 // The work-group -> tile map and the argument contract of the entry points are the f16x2 kernels' own: one definition each, in
 // gemm_split_shared.h.
 //
-// Small row counts: there is no split-K variant of this kernel.  The caller keeps rows <= SPLITK_MAX_ROWS on the f16x2 split-K route
-// (ops.py, mmdit.py).
+// Small row counts: by default the caller keeps rows <= SPLITK_MAX_ROWS on the f16x2 split-K route (ops.py, mmdit.py); the opt-in split-K
+// form of this kernel is gemm_f16_splitk.hip (its own kernel text: this file's code object stays as it is).
 #include "common.h"
 #include "gemm_split_shared.h"
 #include "selftok_hip_ext.h"

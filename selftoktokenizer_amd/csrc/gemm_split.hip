@@ -767,6 +767,31 @@ int selftok_linear_f16x2_split_residual(const void* a_blk, const void* packed, c
     return check_launch("linear_f16x2_pre_kernel(residual)");
 }
 
+}  // extern "C"
+
+// second launch of a split-K Linear, for the f16x2 entries below and the f16 ones of gemm_f16_splitk.hip (gemm_split_shared.h).  It stands
+// HERE, and names the plain forms before the residual one, because hipcc emits kernels in the order of their first use: the code object
+// keeps the order it had when the two entries below launched splitk_finish_kernel themselves.
+int selftok::launch_splitk_finish(const float* ws, int ksplit, const float* bias, float* out, void* out_blk, long ldo, int M, int N, int flags,
+                                  int* overflow, const ResArgs* res, hipStream_t stream)
+{
+    const long n = (long)M * (N / 8);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (!res) {
+        const bool osplit = out_blk != nullptr;
+        _Float16* ob = (_Float16*)out_blk;
+#define FIN_LAUNCH(ACT, OS) hipLaunchKernelGGL((splitk_finish_kernel<ACT, OS, 0>), grid, dim3(256), 0, stream, ws, ksplit, bias, out, ob, ldo, M, N, overflow, ResArgs{})
+        if (flags & SELFTOK_LINEAR_GELU) { if (osplit) FIN_LAUNCH(1, 1); else FIN_LAUNCH(1, 0); }
+        else { if (osplit) FIN_LAUNCH(0, 1); else FIN_LAUNCH(0, 0); }
+#undef FIN_LAUNCH
+        return check_launch("splitk_finish_kernel");
+    }
+    hipLaunchKernelGGL((splitk_finish_kernel<0, 0, 1>), grid, dim3(256), 0, stream, ws, ksplit, bias, out, (_Float16*)nullptr, ldo, M, N, overflow, *res);
+    return check_launch("splitk_finish_kernel(residual)");
+}
+
+extern "C" {
+
 size_t selftok_linear_f16x2_splitk_workspace_bytes(int M, int N, int ksplit)
 {
     if (M <= 0 || N <= 0 || ksplit <= 1) return 0;
@@ -780,17 +805,9 @@ int selftok_linear_f16x2_split_k(const void* a_blk, const void* packed, const fl
     int rc = check_split_linear("linear_f16x2_split_k", a_blk, packed, bias, out, out_blk, ldo, M, N, K);
     if (rc != SELFTOK_OK || M == 0) return rc;
     if ((rc = check_splitk("linear_f16x2_split_k", K, ksplit, workspace))) return rc;
-    const bool osplit = out_blk != nullptr;
     float* ws = (float*)workspace;
     if (int rc = launch_splitk_partials(a_blk, packed, ws, M, N, K, ksplit, overflow, stream)) return rc;
-    const long n = (long)M * (N / 8);
-    const dim3 grid((unsigned)((n + 255) / 256));
-    _Float16* ob = (_Float16*)out_blk;
-#define FIN_LAUNCH(ACT, OS) hipLaunchKernelGGL((splitk_finish_kernel<ACT, OS, 0>), grid, dim3(256), 0, stream, (const float*)ws, ksplit, bias, out, ob, ldo, M, N, overflow, ResArgs{})
-    if (flags & SELFTOK_LINEAR_GELU) { if (osplit) FIN_LAUNCH(1, 1); else FIN_LAUNCH(1, 0); }
-    else { if (osplit) FIN_LAUNCH(0, 1); else FIN_LAUNCH(0, 0); }
-#undef FIN_LAUNCH
-    return check_launch("splitk_finish_kernel");
+    return launch_splitk_finish(ws, ksplit, bias, out, out_blk, ldo, M, N, flags, overflow, nullptr, stream);
 }
 
 int selftok_linear_f16x2_split_residual_k(const void* a_blk, const void* packed, const float* bias,
@@ -804,10 +821,8 @@ int selftok_linear_f16x2_split_residual_k(const void* a_blk, const void* packed,
     if ((rc = check_splitk("linear_f16x2_split_residual_k", K, ksplit, workspace))) return rc;
     float* ws = (float*)workspace;
     if (int rc = launch_splitk_partials(a_blk, packed, ws, M, N, K, ksplit, overflow, stream)) return rc;
-    const long n = (long)M * (N / 8);
-    hipLaunchKernelGGL((splitk_finish_kernel<0, 0, 1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)ws, ksplit, bias, out,
-                       (_Float16*)nullptr, ldo, M, N, overflow, ResArgs{resid, ldr, gate, gate_stride_b, gate_stride_t, T});
-    return check_launch("splitk_finish_kernel(residual)");
+    const ResArgs res{resid, ldr, gate, gate_stride_b, gate_stride_t, T};
+    return launch_splitk_finish(ws, ksplit, bias, out, nullptr, ldo, M, N, 0, overflow, &res, stream);
 }
 
 }  // extern "C"

@@ -127,11 +127,17 @@ inline int check_split_linear_residual(const char* who, const void* a_blk, const
     return SELFTOK_OK;
 }
 
-// split-K (the f16x2 _k entries): 2 .. 64 parts, each a whole number of k-tiles, and a workspace to put them in
+// split-K (the f16x2 and f16 _k entries): 2 .. 64 parts, each a whole number of k-tiles, and a workspace to put them in
 inline int check_splitk(const char* who, int K, int ksplit, const void* workspace)
 {
     if (ksplit >= 2 && ksplit <= 64 && (K / BK) % ksplit == 0 && workspace && !((size_t)workspace & 15)) return SELFTOK_OK;
     return refuse_args(who, "ksplit not in 2..64 / not a divisor of K / 32, or no 16-byte aligned workspace");
 }
+
+// second launch of every split-K Linear (defined in gemm_split.hip, next to splitk_finish_kernel): out = epilogue(sum of the `ksplit` planes
+// [M][N] of `ws` in ascending order + bias).  `res` == nullptr: flags (SELFTOK_LINEAR_GELU) and fp32 `out` or the split output `out_blk`;
+// otherwise the fused residual update into `out`.  Arguments already checked by the entry.
+int launch_splitk_finish(const float* ws, int ksplit, const float* bias, float* out, void* out_blk, long ldo, int M, int N, int flags,
+                         int* overflow, const ResArgs* res, hipStream_t stream);
 
 }  // namespace selftok

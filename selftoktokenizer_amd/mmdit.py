@@ -39,11 +39,13 @@ class MMDiTGPU(ModuleSurface):
     PRESPLIT = True     # f16x2 mode: producers (LN-modulate, attention, fc1+GELU) hand the next Linear its input already split
     SPLITK = True       # f16x2 mode, <= ops.SPLITK_MAX_ROWS rows (one .. four images): several work-groups per output tile (ops.f16x2_ksplit)
     ATTENTION_MODES = ("split", "f16")   # arithmetic of the joint attention in the split GEMM modes; 'f16' (LOSSY) only with gemm='f16'
+    SPLITK_MODES = ("f16x2", "f16")      # arithmetic of the block Linears at <= ops.SPLITK_MAX_ROWS rows in the split GEMM modes; 'f16' (LOSSY) only with gemm='f16'
 
     def __init__(self, sd: Dict[str, torch.Tensor], device, K: int, renderer: bool = False, gemm: str = "fp32"):
         self.device, self.K, self.renderer = device, K, renderer
         self.gemm = "fp32"
         self.attention = "split"                                            # 'f16': the joint attention on ops.ATTN_F16 (set_gemm('f16', attention='f16'))
+        self.splitk = "f16x2"                                               # 'f16': rows <= ops.SPLITK_MAX_ROWS on ops.linear_f16_split_k (set_gemm('f16', splitk='f16'))
         self._packed = {}                                                   # linear name -> f16x2-split weight image
         self._mod_cache = {}                                                # (timestep name, gemm mode) -> modulations of a single-image step
         self._capture_refs = None                                           # list while a caller captures a hipGraph (see _step_modulations)
@@ -70,7 +72,7 @@ class MMDiTGPU(ModuleSurface):
             self.set_gemm(gemm)
 
     # ---- GEMM arithmetic of the block Linears ---------------------------------------------------
-    def set_gemm(self, mode: str, attention: Optional[str] = None) -> str:
+    def set_gemm(self, mode: str, attention: Optional[str] = None, splitk: Optional[str] = None) -> str:
         """'fp32': hipBLASLt fp32 GEMMs (PyTorch-ROCm) + the fp32-input-MFMA attention kernel.  'f16x2': the qkv / proj / fc1 / fc2
         Linears of the 24 joint blocks (99.6 % of the decode FLOPs) run on ops.linear_f16x2 and the joint attention on
         attn64_f16x2_kernel -- fp32-equivalent split arithmetic on the f16 matrix cores, measured MORE accurate against fp64 than the
@@ -80,11 +82,15 @@ class MMDiTGPU(ModuleSurface):
         'f16' (LOSSY, labelled: outside the 1e-3 dB of the other modes): everything of 'f16x2' -- the same packed weight
         images, the same split-activation producers, the same f16x2 joint attention, the same range refusal and overflow flag -- except that
         the block Linears above ops.SPLITK_MAX_ROWS rows run ops.linear_f16_split: fp16-rounded operands (the hi planes alone), fp32
-        accumulation, one matrix instruction per product.  Rows <= SPLITK_MAX_ROWS stay on the f16x2 split-K route (the single-pass fp16
-        kernel has no split-K variant).
+        accumulation, one matrix instruction per product.  Rows <= SPLITK_MAX_ROWS stay on the f16x2 split-K route unless `splitk` says
+        otherwise: one to four images then decode with f16x2 bits.
         `attention` (opt-in, LOSSY): None or 'split' is the attention described above; 'f16' -- legal only together with
         mode 'f16', ValueError otherwise -- runs every joint-attention call, at every row count, on the single-pass fp16 kernel
-        (ops.ATTN_F16, csrc/attention_f16.hip).  A call without the argument resets it.  Returns the mode in force."""
+        (ops.ATTN_F16, csrc/attention_f16.hip).  A call without the argument resets it.
+        `splitk` (opt-in, LOSSY): None or 'f16x2' is the route described above; 'f16' -- legal only together with mode
+        'f16', ValueError otherwise -- sends the block Linears with rows <= SPLITK_MAX_ROWS to the split-K form of the single-pass fp16
+        kernel (ops.linear_f16_split_k with ops.f16_ksplit, csrc/gemm_f16_splitk.hip).  A call without the argument resets it.
+        Returns the mode in force."""
         if mode not in self.GEMM_MODES:
             raise ValueError(f"gemm mode {mode!r}: expected one of {self.GEMM_MODES}")
         attention = "split" if attention is None else attention
@@ -92,6 +98,11 @@ class MMDiTGPU(ModuleSurface):
             raise ValueError(f"attention {attention!r}: expected None or one of {self.ATTENTION_MODES}")
         if attention == "f16" and mode != "f16":
             raise ValueError(f"attention='f16' is the attention of the lossy gemm mode 'f16', not of {mode!r}")
+        splitk = "f16x2" if splitk is None else splitk
+        if splitk not in self.SPLITK_MODES:
+            raise ValueError(f"splitk {splitk!r}: expected None or one of {self.SPLITK_MODES}")
+        if splitk == "f16" and mode != "f16":
+            raise ValueError(f"splitk='f16' is the small-batch route of the lossy gemm mode 'f16', not of {mode!r}")
         if mode == "exact":
             self._build_exact()
         self.ctx_tables = self._tables_exact if mode == "exact" else self._tables_fast
@@ -110,6 +121,7 @@ class MMDiTGPU(ModuleSurface):
                 self._packed = packed
         self.gemm = mode
         self.attention = attention if mode == "f16" else "split"          # a refused 'f16' (weights out of range) falls back with the mode
+        self.splitk = splitk if mode == "f16" else "f16x2"                # and so does the small-batch route
         return mode
 
     # ---- 'exact': every Linear / LayerNorm / GELU / SiLU / attention as the sequence of fp32 operations torch-CPU executes for the reference ----
@@ -154,7 +166,7 @@ class MMDiTGPU(ModuleSurface):
             return self._lin_split(name, x, gelu=gelu, out_split=out_split)
         assert not out_split
         if self.gemm in self.SPLIT_MODES and name in self._packed:
-            if self._single_f16(x.numel() // x.shape[-1]):
+            if self._single_f16(x.numel() // x.shape[-1]) or self._f16_splitk():      # the fp16 kernels take split input only
                 return self._lin_split(name, ops.split_f16x2(x, self.overflow), gelu=gelu)
             return ops.linear_f16x2(x, self._packed[name], b, w.shape[0], gelu=gelu, overflow=self.overflow)
         if gelu:
@@ -162,13 +174,17 @@ class MMDiTGPU(ModuleSurface):
         return F.linear(x, w, b)
 
     def _lin_split(self, name, xs, **epilogue):
-        """the packed Linear `name` on a split activation: the route (single-pass fp16 kernel, or the f16x2 kernels with which ksplit) chosen
-        here and nowhere else.  `epilogue`: gelu / out_split, or resid / gate / gate_per_sample (the fused residual update)."""
+        """the packed Linear `name` on a split activation: the route (single-pass fp16 kernel, its split-K form with which ksplit, or the f16x2
+        kernels with which ksplit) chosen here and nowhere else.  `epilogue`: gelu / out_split, or resid / gate / gate_per_sample (the fused
+        residual update)."""
         assert name in self._packed, f"split activation handed to Linear {name!r}, which has no f16x2-split weight (set_gemm('f16x2') packs the block Linears)"
         w, b = self.w[name + ".weight"], self.w[name + ".bias"]
         residual = "resid" in epilogue
         if self._single_f16(xs.rows):
             fn = ops.linear_f16_split_residual if residual else ops.linear_f16_split
+        elif self._f16_splitk():                                # opt-in: small row counts stay in the lossy arithmetic
+            fn = ops.linear_f16_split_residual_k if residual else ops.linear_f16_split_k
+            epilogue["ksplit"] = ops.f16_ksplit(xs.rows, w.shape[0], w.shape[1]) if self.SPLITK else 1
         else:
             fn = ops.linear_f16x2_split_residual if residual else ops.linear_f16x2_split
             epilogue["ksplit"] = self._ksplit(xs.rows, w)
@@ -180,6 +196,10 @@ class MMDiTGPU(ModuleSurface):
     def _single_f16(self, rows: int) -> bool:
         """'f16' mode: does a packed Linear over `rows` rows run the single-pass fp16 kernel?  Small row counts keep the f16x2 split-K route."""
         return self.gemm == "f16" and rows > ops.SPLITK_MAX_ROWS
+
+    def _f16_splitk(self) -> bool:
+        """'f16' mode with splitk='f16': do the packed Linears that `_single_f16` leaves (rows <= SPLITK_MAX_ROWS) run the split-K fp16 kernel?"""
+        return self.gemm == "f16" and self.splitk == "f16"
 
     def _pre(self, name) -> bool:
         """does Linear `name` take its input as a split activation?"""

@@ -400,19 +400,22 @@ def f16x2_ksplit(M: int, N: int, K: int) -> int:
 
 
 def _linear_split(xs: SplitAct, packed: torch.Tensor, bias, N: int, *, single_pass: bool, gelu: bool = False, out_split: bool = False, resid=None,
-                  gate=None, gate_per_sample: bool = False, ksplit: int = 1, overflow: torch.Tensor = None):
-    """the Linear on a split activation, every form: `single_pass` = the fp16 kernel (csrc/gemm_f16.hip; no split-K) instead of the f16x2
-    kernels (csrc/gemm_split.hip, `ksplit` parts along K); epilogue = `gelu` / `out_split`, or with `resid` [B,T,N] the fused residual
-    update resid + gate * y.  Returns fp32 [..., N], a SplitAct [..., N], or a tensor like resid."""
+                  gate=None, gate_per_sample: bool = False, ksplit: Optional[int] = None, overflow: torch.Tensor = None):
+    """the Linear on a split activation, every form.  Arithmetic: `single_pass` = the fp16 kernels (hi planes only, LOSSY) instead of the f16x2
+    kernels.  Route along K, four combinations: f16x2 -> the _k entries of csrc/gemm_split.hip with `ksplit` parts (None = 1, their single
+    launch); single_pass with ksplit None -> the plain entries of csrc/gemm_f16.hip; single_pass with a `ksplit` -> the _k entries of
+    csrc/gemm_f16_splitk.hip (1 forwards to the plain entry inside the library).  Epilogue = `gelu` / `out_split`, or with `resid` [B,T,N] the
+    fused residual update resid + gate * y.  Returns fp32 [..., N], a SplitAct [..., N], or a tensor like resid."""
     _need_cuda(xs.data, packed, resid)
     K = xs.shape[-1]
     assert packed.numel() * 2 == 4 * N * K, "packed weight does not match (N, K)"
-    assert not (single_pass and ksplit != 1), "the single-pass fp16 kernel has no split-K variant"
     M, lead = xs.rows, xs.shape[:-1]
     lib = _lib.load()
     name = "selftok_linear_f16_split" if single_pass else "selftok_linear_f16x2_split"
     tail = (_p(overflow), _stream())
-    if not single_pass:                                   # the _k entries; ksplit == 1 is their single launch
+    k_entry = not single_pass or ksplit is not None       # the _k entries; ksplit == 1 is their single launch
+    if k_entry:
+        ksplit = 1 if ksplit is None else int(ksplit)
         ws = torch.empty(ksplit * M * N, dtype=torch.float32, device=xs.device) if (ksplit > 1 and M > 0) else None
         tail = (ksplit, _p(ws)) + tail
     if resid is not None:
@@ -422,11 +425,11 @@ def _linear_split(xs: SplitAct, packed: torch.Tensor, bias, N: int, *, single_pa
         assert M == B * T
         gsb, gst = _table_strides(gate, gate_per_sample, B, T, N)
         out = torch.empty_like(resid)
-        name += "_residual" if single_pass else "_residual_k"
+        name += "_residual_k" if k_entry else "_residual"
         _lib.check(getattr(lib, name)(_p(xs.data), _p(packed), _p(bias), _p(resid), N, _p(gate), gsb, gst, T, _p(out), N, M, N, K, *tail), name)
         return out
     out = SplitAct((*lead, N), xs.device) if out_split else torch.empty(M, N, dtype=torch.float32, device=xs.device)
-    name += "" if single_pass else "_k"
+    name += "_k" if k_entry else ""
     _lib.check(getattr(lib, name)(_p(xs.data), _p(packed), _p(bias), None if out_split else _p(out), _p(out.data) if out_split else None, N, M, N, K,
                                   LINEAR_GELU if gelu else 0, *tail), name)
     return out if out_split else out.reshape(*lead, N)
@@ -461,8 +464,9 @@ def linear_f16_split(xs, packed: torch.Tensor, bias, N: int, gelu: bool = False,
     operands, one matrix instruction per product instead of three.  LOSSY (11 significand bits per operand), not fp32-equivalent.
     `xs`: a SplitAct, or an fp32 tensor [..., K] (fed through split_f16x2); `packed`: linear_f16x2_pack(W), the same image the
     f16x2 mode holds -- only the hi planes of both are read.  Returns fp32 [..., N], or with out_split a SplitAct with both planes.
-    On fp16-representable operands the result equals linear_f16x2_split's.  There is no split-K variant of this kernel: callers
-    keep row counts <= SPLITK_MAX_ROWS on linear_f16x2_split(..., ksplit=f16x2_ksplit(...)) (MMDiTGPU.lin does)."""
+    On fp16-representable operands the result equals linear_f16x2_split's.  This entry walks all of K in one work-group per tile: by
+    default callers keep row counts <= SPLITK_MAX_ROWS on linear_f16x2_split(..., ksplit=f16x2_ksplit(...)) (MMDiTGPU.lin does); the
+    opt-in split-K form in this arithmetic is linear_f16_split_k."""
     return _linear_split(_as_split(xs, overflow), packed, bias, N, single_pass=True, gelu=gelu, out_split=out_split, overflow=overflow)
 
 
@@ -471,6 +475,50 @@ def linear_f16_split_residual(xs, packed: torch.Tensor, bias, N: int, resid: tor
     """resid + gate * linear_f16_split(xs): the fused residual epilogue of linear_f16x2_split_residual (same operations, same order)
     on the single-pass fp16 product.  Arguments as there; `xs` may be an fp32 tensor."""
     return _linear_split(_as_split(xs, overflow), packed, bias, N, single_pass=True, resid=resid, gate=gate, gate_per_sample=gate_per_sample, overflow=overflow)
+
+
+# the cost model of f16_ksplit, fitted to profiles/f16_splitk_sweep.txt (tools/sweep_splitk.py --f16): us per k-tile of the longest chain,
+# us per fp32 partial written and re-read, us for the second launch, fewest k-tiles per part.  None: no sweep yet -> f16x2_ksplit's choice.
+# The fit: over the 16 swept (rows, Linear) cases the choice costs 1.4 us in all over the best swept split, 3 % at worst (qkv at 256 rows);
+# a k-tile costs about half of what it costs the f16x2 kernel (0.42 us), so fewer parts pay for their partial planes than there.
+F16_SPLITK_COST = (0.23, 1.2e-6, 2.0, 3)
+
+
+@functools.lru_cache(maxsize=4096)
+def f16_ksplit(M: int, N: int, K: int) -> int:
+    """how many work-groups should share an output tile of a [M, K] x [K, N] Linear on the single-pass fp16 split-K kernel
+    (linear_f16_split_k): the divisor rule of f16x2_ksplit -- a divisor of K / 32 in 1 .. 64 that keeps the grid within one work-group per
+    CU, 1 above SPLITK_MAX_ROWS -- with the cost constants of F16_SPLITK_COST.  A pure function of (M, N, K, CU count)."""
+    if M <= 0 or M > SPLITK_MAX_ROWS:
+        return 1
+    if F16_SPLITK_COST is None:
+        return f16x2_ksplit(M, N, K)
+    per_tile, per_partial, second, min_tiles = F16_SPLITK_COST
+    tiles = ((M + 255) // 256) * (N // 128)
+    kt = K // 32
+    cus = _cu_count()
+    best, best_cost = 1, per_tile * kt
+    for s in range(2, 65):
+        if kt % s or kt // s < min_tiles or tiles * s > cus:
+            continue
+        cost = per_tile * (kt // s) + per_partial * s * M * N + second
+        if cost < best_cost:
+            best, best_cost = s, cost
+    return best
+
+
+def linear_f16_split_k(xs, packed: torch.Tensor, bias, N: int, ksplit: int, gelu: bool = False, overflow: torch.Tensor = None, out_split: bool = False):
+    """linear_f16_split with `ksplit` work-groups per output tile and a reduction launch (selftok_linear_f16_split_k, csrc/gemm_f16_splitk.hip):
+    for row counts <= SPLITK_MAX_ROWS, ksplit = f16_ksplit(M, N, K).  LOSSY like linear_f16_split, deterministic; with r = fp16 rounding
+    equal to linear_f16x2_split(r(x), pack(r(W)), ksplit=ksplit) bit for bit.  ksplit must divide K / 32 and be <= 64; 1 is linear_f16_split."""
+    return _linear_split(_as_split(xs, overflow), packed, bias, N, single_pass=True, gelu=gelu, out_split=out_split, ksplit=int(ksplit), overflow=overflow)
+
+
+def linear_f16_split_residual_k(xs, packed: torch.Tensor, bias, N: int, resid: torch.Tensor, ksplit: int, gate=None,
+                                gate_per_sample: bool = False, overflow: torch.Tensor = None) -> torch.Tensor:
+    """resid + gate * linear_f16_split_k(xs): linear_f16_split_residual with `ksplit` parts along K (selftok_linear_f16_split_residual_k)."""
+    return _linear_split(_as_split(xs, overflow), packed, bias, N, single_pass=True, resid=resid, gate=gate, gate_per_sample=gate_per_sample,
+                         ksplit=int(ksplit), overflow=overflow)
 
 
 def silu(x):

@@ -161,7 +161,8 @@ class SelftokPipeline():
                  dtype=torch.bfloat16, ema_decoder=False, device=None, state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  vae_state_dict: Optional[Dict[str, torch.Tensor]] = None, verbose: bool = True, gemm: Optional[str] = None,
                  vae_mode: Optional[str] = None, tune_gemm: Optional[bool] = None, encoder_mode: Optional[str] = None,
-                 vae_encode_mode: Optional[str] = None, vae_decode_mode: Optional[str] = None, attention: Optional[str] = None):
+                 vae_encode_mode: Optional[str] = None, vae_decode_mode: Optional[str] = None, attention: Optional[str] = None,
+                 splitk: Optional[str] = None):
         """cfg: parse_args_from_yaml(...) ; ckpt_path: tokenizer .pth ; sd3_path: diffusers SD3 folder (…/vae/…).
         `state_dict` / `vae_state_dict` (extensions) bypass the files, e.g. with weights.synthetic_state_dict().
         `gemm` (extension): arithmetic of the MMDiT block Linears, 'fp32' (hipBLASLt fp32), 'f16x2' (fp32-equivalent
@@ -169,6 +170,9 @@ class SelftokPipeline():
         operands, fp32 accumulation, csrc/gemm_f16.hip -- for bulk decoding, outside the north star's 1e-3 dB); default DEFAULT_GEMM.
         `attention` (extension, OPT-IN, LOSSY): None / 'split' (default), or 'f16' together with gemm='f16' -- the joint attention of the MMDiT and the renderer
         as one fp16 matrix instruction per product (csrc/attention_f16.hip); ValueError with any other gemm mode.
+        `splitk` (extension, OPT-IN, LOSSY): None / 'f16x2' (default: in gemm='f16' one to four images decode on the f16x2 split-K Linears, with f16x2 bits), or
+        'f16' together with gemm='f16' -- those row counts on the split-K form of the single-pass fp16 Linear (csrc/gemm_f16_splitk.hip); ValueError with any
+        other gemm mode.
         `vae_encode_mode` / `vae_decode_mode` (extensions; `vae_mode` sets both): arithmetic of the two halves of the SD3 VAE (vae.AutoencoderKLGPU).
         'exact': every reduction in the summation ORDER of the reference's torch-CPU run (csrc/vae_exact.hip, fp32 matrix cores) -- encoder: latents and
         token ids from pixels equal the reference's bit for bit; decoder: pixels equal the reference's decode of the same latents, incl. its batch
@@ -204,12 +208,14 @@ class SelftokPipeline():
             self.device = torch.device("cuda", torch.cuda.current_device())
         with torch.cuda.device(self.device):                                  # our launches use the current device's stream
             self._build(cfg, ckpt_path, sd3_path, start, cfg_scale, dtype, ema_decoder, state_dict, vae_state_dict, verbose, gemm, vae_mode, encoder_mode,
-                        vae_encode_mode, vae_decode_mode, attention)
+                        vae_encode_mode, vae_decode_mode, attention, splitk)
 
     def _build(self, cfg, ckpt_path, sd3_path, start, cfg_scale, dtype, ema_decoder, state_dict, vae_state_dict, verbose, gemm, vae_mode=None, encoder_mode=None,
-               vae_encode_mode=None, vae_decode_mode=None, attention=None):
+               vae_encode_mode=None, vae_decode_mode=None, attention=None, splitk=None):
         if attention == "f16" and (gemm or DEFAULT_GEMM) != "f16" or attention not in (None,) + MMDiTGPU.ATTENTION_MODES:
             raise ValueError(f"attention={attention!r} with gemm={gemm or DEFAULT_GEMM!r}: expected None, 'split', or 'f16' together with gemm='f16'")
+        if splitk == "f16" and (gemm or DEFAULT_GEMM) != "f16" or splitk not in (None,) + MMDiTGPU.SPLITK_MODES:
+            raise ValueError(f"splitk={splitk!r} with gemm={gemm or DEFAULT_GEMM!r}: expected None, 'f16x2', or 'f16' together with gemm='f16'")
         p = cfg.tokenizer.params
         p.noise_schedule_config.is_eval = cfg.common.is_eval
         # configuration knobs the reference honours but this hot path does not implement: refuse, never ignore silently
@@ -248,7 +254,7 @@ class SelftokPipeline():
             dit_sd = {"model." + k: v for k, v in sd["ema_state_dict"].items()}       # strict contract checked above: bare MMDiT keys only
         encoder = QformerEncoderGPU(sd, self.device, K, mode=encoder_mode or "exact", pre_norm=pre_norm)
         dit = MMDiTGPU(dit_sd, self.device, K, renderer=renderer)
-        dit.set_gemm(gemm or DEFAULT_GEMM, attention=attention)
+        dit.set_gemm(gemm or DEFAULT_GEMM, attention=attention, splitk=splitk)
         self.model = _Tokenizer(encoder, dit, self.diti)
 
         self.count = 0
@@ -261,7 +267,7 @@ class SelftokPipeline():
         self.k_table = self.diti.to_indices(self.flow.t_long)                # k for each of the 50 steps
         self.cond_vary = True
         self.saved_images = 8
-        self._graphs = {}        # (shapes, steps, scale, gemm, attention, context plan) -> (hipGraph, static noise, static ehs, static output, what the graph reads)
+        self._graphs = {}        # (shapes, steps, scale, gemm, attention, splitk, context plan) -> (hipGraph, static noise, static ehs, static output, what the graph reads)
 
     def _say(self, msg):
         if self.verbose:          # the reference prints these progress lines unconditionally (:192,212,223,230,292,299,320)
@@ -373,12 +379,13 @@ class SelftokPipeline():
         import contextlib
         return gemm_tune.enabled() if (self.tune_gemm and self.gemm_tune_report and self.model.model.gemm == "fp32") else contextlib.nullcontext()
 
-    def set_gemm(self, mode: str, attention: Optional[str] = None) -> str:
+    def set_gemm(self, mode: str, attention: Optional[str] = None, splitk: Optional[str] = None) -> str:
         """switch the MMDiT between 'fp32', 'f16x2', 'exact' and the lossy 'f16' (see MMDiTGPU.set_gemm); returns the mode in force.  Unless the decoder's arithmetic was
         chosen explicitly (`vae_decode_mode` / `vae_mode`), 'exact' brings the exact-order VAE decoder with it (the mode whose pixels are the reference's
         bit for bit) and the other modes return to the default decoder.  `attention`: None / 'split', or 'f16' together with mode 'f16' (LOSSY single-pass
-        fp16 joint attention, MMDiTGPU.set_gemm); a call without it resets it."""
-        got = self.model.model.set_gemm(mode, attention=attention)
+        fp16 joint attention, MMDiTGPU.set_gemm); a call without it resets it.  `splitk`: None / 'f16x2', or 'f16' together with mode 'f16' (LOSSY: one to four
+        images on the split-K single-pass fp16 Linears instead of the f16x2 ones, MMDiTGPU.set_gemm); a call without it resets it."""
+        got = self.model.model.set_gemm(mode, attention=attention, splitk=splitk)
         if not self._vae_decode_explicit and self.vae.mode in ("exact", "parity"):
             want = "exact" if (got == "exact" and int(self.datasize) in AutoencoderKLGPU.EXACT_SIZES) else DEFAULT_VAE_DECODE
             if self.vae.decode_mode != want:
@@ -391,7 +398,7 @@ class SelftokPipeline():
         result (sticky device flag, one host read per call): redo the call on the fp32 library GEMMs."""
         dit = self.model.model
         out = run()
-        mode, attention = dit.gemm, dit.attention
+        mode, attention, splitk = dit.gemm, dit.attention, dit.splitk
         if mode in dit.SPLIT_MODES and int(dit.overflow.item()) != 0:
             print(f"[selftok] {mode} GEMM: activation outside the fp16 range -> recomputing this call with fp32 GEMMs")
             dit.overflow.zero_()
@@ -399,7 +406,7 @@ class SelftokPipeline():
             try:
                 out = run()
             finally:
-                dit.set_gemm(mode, attention=attention)    # the split weights are kept: no re-pack
+                dit.set_gemm(mode, attention=attention, splitk=splitk)    # the split weights are kept: no re-pack
         return out
 
     @torch.no_grad()
@@ -426,7 +433,7 @@ class SelftokPipeline():
         loop = lambda noise, e: self.flow.p_sample_loop(dit, noise, e, self.k_table, context_see_xt=True, uncond_scale=uncond_scale, max_steps=max_steps, plan=plan)
         if not use_graph:
             return loop(xt, ehs)
-        key = (tuple(xt.shape), tuple(ehs.shape), max_steps, float(uncond_scale), dit.gemm, dit.attention, dit.PRESPLIT, dit.SPLITK, plan[0].key)
+        key = (tuple(xt.shape), tuple(ehs.shape), max_steps, float(uncond_scale), dit.gemm, dit.attention, dit.splitk, dit.PRESPLIT, dit.SPLITK, plan[0].key)
         if key not in self._graphs:
             s_noise = torch.empty(xt.shape, dtype=torch.float32, device=self.device)
             s_ehs = torch.empty_like(ehs)
