@@ -61,6 +61,28 @@ int selftok_img_resize_tables_layout(const long* table_host, int B, int S, long*
 int selftok_img_resize_crop_norm_u8(const unsigned char* packed, size_t packed_bytes, const long* table_host, const long* table_dev, int B, int S, void* out,
                                     int out_bf16, const void* lut, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* ---- device image views: crop box -> resize -> S x S window -> flip -> NormalizeToTensor, PIL-exact ----
+ * V outputs [V, 3, S, S] taken from RGB uint8 HWC sources packed into one device buffer; several views may name the same source, which
+ * lies in `packed` once.  One row of twelve longs per OUTPUT: byte offset of the source, its width W and height H; the crop box x0, y0,
+ * bw, bh; the size Rw, Rh the box is resized to; the window's left, top inside Rw x Rh; flip (0 or 1).  Per view, bit for bit:
+ *   im = source.crop((x0, y0, x0 + bw, y0 + bh)); im = im.resize((Rw, Rh), BILINEAR) unless (Rw, Rh) == (bw, bh);
+ *   im = im.crop((left, top, left + S, top + S)); im = im.transpose(FLIP_LEFT_RIGHT) if flip; out = lut[im]
+ * with the resample of selftok_img_resize_crop_norm_u8 (horizontal pass first, uint8 between the passes, fp64 weights, 22-bit
+ * coefficients, (2^21 + sum) >> 22, clip; an axis whose length does not change is not resampled).  Crop-then-resize, as torchvision's
+ * resized_crop does it: NOT Pillow's resize(box=), whose taps reach outside the box.  Only the window is resampled; the flip is a
+ * reversed column index at the store.  torchvision's FiveCrop / TenCrop / RandomResizedCrop / hflip are choices of these numbers.
+ * The table is passed twice like the table of selftok_img_resize_crop_norm_u8 and under the same rule: the host copy is validated
+ * (SELFTOK_EINVAL with a message, nothing launched), the device re-checks ITS copy against the limits and the sizes the host copy gave
+ * the launch, and a view that disagrees is skipped: its output planes stay untouched, nothing is read or written outside, return 0.
+ * Limits: 1 <= V <= 65535, 1 <= S <= 4096, 1 <= W, H <= 65536, the box inside the source with bw, bh >= 1, S <= Rw, Rh < 2^30, the window
+ * inside Rw x Rh, offset + 3 * W * H <= packed_bytes.  `lut`, out_bf16, the workspace query and the tap rows left in the workspace
+ * (per view v and window index i, at hdr + (v * S + i) * ks, box coordinates) are those of the entry above, with
+ * selftok_img_views_tables_layout giving hdr / ks. */
+size_t selftok_img_views_u8_workspace_bytes(const long* views_host, int V, int S);
+int selftok_img_views_tables_layout(const long* views_host, int V, int S, long* layout4);
+int selftok_img_views_u8(const unsigned char* packed, size_t packed_bytes, const long* views_host, const long* views_dev, int V, int S, void* out, int out_bf16,
+                         const void* lut, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* ---- device image output: [B, 3, H, W] in [0, 1] -> uint8 [B, H, W, 3] ---------------------------------
  * torchvision.utils.save_image's arithmetic in the tensor's own type: x * 255 rounded to the type, + 0.5 rounded to the type, clamp to
  * [0, 255], truncate.  in_bf16 != 0: bf16 input, else fp32.  +Inf -> 255, -Inf -> 0; NaN -> 0 (this project's choice: torch's

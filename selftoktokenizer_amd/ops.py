@@ -1162,6 +1162,71 @@ def image_resize_crop_norm(packed: torch.Tensor, table, size: int, dtype=torch.b
     return out, tabs
 
 
+def image_view_rows(sources_table, views):
+    """`sources_table` [N, 3] (byte offset, width, height) and `views` [V, 10] (source index, x0, y0, bw, bh, rw, rh, left, top, flip) -> the
+    int64 [V, 12] descriptor table of selftok_img_views_u8, one row per output"""
+    import numpy as np
+    src = _img_table(sources_table)
+    v = np.ascontiguousarray(np.asarray(views), dtype=np.int64)
+    if v.ndim != 2 or v.shape[1] != 10:
+        raise _lib.SelftokHipError(f"image views: expected [V, 10] (source index, x0, y0, bw, bh, rw, rh, left, top, flip), got {v.shape}")
+    if v.shape[0] and (v[:, 0].min() < 0 or v[:, 0].max() >= src.shape[0]):
+        raise _lib.SelftokHipError(f"image views: a source index outside 0 .. {src.shape[0] - 1}")
+    return np.ascontiguousarray(np.concatenate([src[v[:, 0]], v[:, 1:]], axis=1))
+
+
+def image_views(packed: torch.Tensor, sources_table, views, size: int, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None,
+                rows_dev: Optional[torch.Tensor] = None, return_tables: bool = False, rows=None):
+    """V views of RGB uint8 HWC sources packed in the 1-D uint8 device tensor `packed` -> [V, 3, size, size] in [-1, 1], bf16 or fp32: per view
+    NormalizeToTensor(hflip?(crop(window)(resize(crop(box)(PIL image))))) bit for bit (preprocess.apply_view_pil; csrc/image_views.hip).
+    `sources_table` [N, 3] on the host: byte offset, width, height of each source; `views` [V, 10] on the host: source index, x0, y0, bw, bh,
+    rw, rh, left, top, flip (preprocess.view_rows).  Several views may name one source.  V = 0 gives an empty tensor.
+    `rows`: image_view_rows(sources_table, views) already built on the host (contiguous int64 numpy [V, 12]); it is then the table of record and
+    `sources_table` / `views` are not read (pass None).  `rows_dev`: the same rows already on the device (int64 [V, 12]), else they are copied
+    here.  `out`: write into this contiguous tensor.  return_tables: also the integer tap rows, {'h' | 'v': (first [V, size], n [V, size], k [V, size, kmax])} (tests)."""
+    import numpy as np
+    _need_cuda(packed, out, rows_dev)
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise _lib.SelftokHipError(f"image_views: `packed` must be a contiguous 1-D uint8 tensor, got {packed.dtype} {tuple(packed.shape)}")
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.SelftokHipError(f"image_views: output dtype {dtype}: expected bfloat16 or float32")
+    if rows is None:
+        t = image_view_rows(sources_table, views)
+    else:
+        t = rows
+        if not isinstance(t, np.ndarray) or t.dtype != np.int64 or t.ndim != 2 or t.shape[1] != 12 or not t.flags["C_CONTIGUOUS"]:
+            raise _lib.SelftokHipError("image_views: `rows` must be the contiguous int64 numpy [V, 12] table of image_view_rows")
+    V, S = t.shape[0], int(size)
+    if out is None:
+        out = torch.empty(V, 3, max(S, 0), max(S, 0), dtype=dtype, device=packed.device)
+    elif out.dtype != dtype or tuple(out.shape) != (V, 3, S, S) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"image_views: `out` must be a contiguous {dtype} [{V}, 3, {S}, {S}] tensor")
+    if V == 0:
+        return (out, {}) if return_tables else out
+    lib = _lib.load()
+    nbytes = lib.selftok_img_views_u8_workspace_bytes(t.ctypes.data, V, S)
+    if nbytes == 0:
+        _lib.check(-1, "selftok_img_views_u8_workspace_bytes")
+    if rows_dev is None:
+        rows_dev = torch.from_numpy(t).to(packed.device)
+    elif rows_dev.dtype != torch.int64 or rows_dev.numel() != 12 * V or not rows_dev.is_contiguous():
+        raise _lib.SelftokHipError("image_views: `rows_dev` must be the contiguous int64 [V, 12] table")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
+    lut = image_norm_lut(packed.device, dtype)
+    _lib.check(lib.selftok_img_views_u8(_p(packed), packed.numel(), t.ctypes.data, _p(rows_dev), V, S, _p(out), int(dtype == torch.bfloat16),
+                                        _p(lut), _p(ws), nbytes, _stream()), "selftok_img_views_u8")
+    if not return_tables:
+        return out
+    lay = np.zeros(4, dtype=np.int64)
+    _lib.check(lib.selftok_img_views_tables_layout(t.ctypes.data, V, S, lay.ctypes.data), "selftok_img_views_tables_layout")
+    wi = ws[:(nbytes // 4) * 4].view(torch.int32).cpu().numpy()
+    tabs = {}
+    for name, base, ks in (("h", int(lay[0]), int(lay[1])), ("v", int(lay[2]), int(lay[3]))):
+        rows = wi[base:base + V * S * ks].reshape(V, S, ks)
+        tabs[name] = (rows[:, :, 0].copy(), rows[:, :, 1].copy(), rows[:, :, 2:].copy())
+    return out, tabs
+
+
 def image_to_u8(img: torch.Tensor) -> torch.Tensor:
     """[B, 3, H, W] in [0, 1], bf16 or fp32 -> uint8 [B, H, W, 3] with torchvision.utils.save_image's arithmetic in the tensor's own dtype
     (x * 255, + 0.5, each rounded to the dtype, clamp to [0, 255], truncate); NaN -> 0"""

@@ -300,30 +300,37 @@ class SelftokPipeline():
 
     @_on_own_device
     @torch.no_grad()
-    def preprocess_u8(self, images, dtype=None) -> torch.Tensor:
+    def preprocess_u8(self, images, dtype=None, views=None) -> torch.Tensor:
         """(extension) uint8 RGB HWC images -- a list of arrays of ANY sizes, or one uint8 tensor [B, H, W, 3] (host or device) -> the
         [B, 3, datasize, datasize] batch `encoding` takes, on the device: Resize(datasize) -> CenterCrop(datasize) -> NormalizeToTensor of
-        the reference's user script (test.py:27-31) bit for bit (csrc/image_io.hip).  dtype: this pipeline's bf16 (default) or fp32."""
+        the reference's user script (test.py:27-31) bit for bit (csrc/image_io.hip).  dtype: this pipeline's bf16 (default) or fp32.
+        views = fn(width, height) -> a list of preprocess.View (views_five, views_ten, view_resized_crop, ...): instead [sum of views, 3,
+        datasize, datasize], image by image and then view by view, each what torchvision gives on the PIL image (preprocess.apply_view_pil)
+        bit for bit (csrc/image_views.hip).  views=None is the centre crop, by the same route as before."""
         dtype = dtype or self.dtype
         if torch.is_tensor(images):
             if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
                 raise TypeError(f"expected a uint8 [B, H, W, 3] tensor, got {images.dtype} {tuple(images.shape)}")
             if images.is_cuda:
                 B, H, W, _ = images.shape
-                table = np.array([[b * H * W * 3, W, H] for b in range(B)], dtype=np.int64)
+                table = np.array([[b * H * W * 3, W, H] for b in range(B)], dtype=np.int64).reshape(B, 3)
+                if views is not None:
+                    from .preprocess import view_rows
+                    return ops.image_views(images.to(self.device).contiguous().reshape(-1), table, view_rows([views(W, H) for _ in range(B)], int(self.datasize)),
+                                           int(self.datasize), dtype=dtype)
                 return ops.image_resize_crop_norm(images.to(self.device).contiguous().reshape(-1), table, int(self.datasize), dtype=dtype)
             images = list(images.numpy())
         loaders = self.__dict__.setdefault("_u8_loaders", {})
         if dtype not in loaders:
             from .preprocess import DeviceLoader
             loaders[dtype] = DeviceLoader(int(self.datasize), self.device, dtype=dtype)
-        return loaders[dtype].load(images)
+        return loaders[dtype].load(images) if views is None else loaders[dtype].load(images, views=views)
 
-    def encoding_u8(self, images, device=None, topk: int = 0):
+    def encoding_u8(self, images, device=None, topk: int = 0, views=None):
         """(extension) `encoding` from 8-bit pixels: equal to encoding(torch.stack([load_image-equivalent of each image])) -- same bf16 tensor
         into the VAE, same token ids -- without the per-image PIL resize, fp32 tensors and pageable copy on the host.  topk = k > 0: the (ids, scores)
-        of `encoding_topk(..., k)` instead."""
-        x = self.preprocess_u8(images)
+        of `encoding_topk(..., k)` instead.  views: see preprocess_u8; one row of ids per view, equal to encoding(torch.stack([apply_view_pil(...)]))."""
+        x = self.preprocess_u8(images) if views is None else self.preprocess_u8(images, views=views)
         return self.encoding_topk(x, k=topk, device=device) if topk else self.encoding(x, device=device)
 
     @_on_own_device

@@ -1,11 +1,13 @@
 """Image pre/post-processing of the reference's user script without torchvision (reference test.py:27-31, 42-43):
 Resize(size) [shorter side, bilinear + antialias on PIL images] -> CenterCrop(size) -> NormalizeToTensor, and
-`save_image` for the [0,1] outputs of `decoding`."""
+`save_image` for the [0,1] outputs of `decoding`; the augmented recipes (FiveCrop / TenCrop / resized_crop / hflip on a PIL image) as
+*views* -- pure integer geometry (`views_five`, `views_ten`, `view_resized_crop`), their PIL route (`apply_view_pil`) and, through
+`DeviceLoader(..., views=fn)`, the same tensors computed on the GPU (csrc/image_views.hip)."""
 from __future__ import annotations
 
 import time
 from concurrent.futures import ThreadPoolExecutor
-from typing import Iterator, Sequence
+from typing import Iterator, NamedTuple, Sequence
 
 import numpy as np
 import torch
@@ -36,6 +38,98 @@ def load_image(path: str, size: int = 256) -> torch.Tensor:
     """-> float tensor [3,size,size] in [-1,1] (what `SelftokPipeline.encoding` takes, stacked along dim 0)."""
     img = Image.open(path).convert("RGB")
     return NormalizeToTensor()(center_crop(resize_shorter_side(img, size), size))
+
+
+# ---- views: torchvision's five / ten-crop, resized_crop and hflip on a PIL image, as numbers (csrc/image_views.hip) ----
+class View(NamedTuple):
+    """one size x size output of one w x h source: source.crop((x0, y0, x0 + bw, y0 + bh)) -> resize to (rw, rh) unless that is (bw, bh) ->
+    crop((left, top, left + size, top + size)) -> FLIP_LEFT_RIGHT if flip.  Pure integers: nothing here draws a random number."""
+    x0: int
+    y0: int
+    bw: int
+    bh: int
+    rw: int
+    rh: int
+    left: int
+    top: int
+    flip: int
+    size: int
+
+
+def _resized_size(w: int, h: int, size: int):
+    """the size `resize_shorter_side` gives"""
+    if (w <= h and w == size) or (h <= w and h == size):
+        return w, h
+    return (size, int(size * h / w)) if w < h else (int(size * w / h), size)
+
+
+def _centre(side: int, size: int) -> int:
+    return int(round((side - size) / 2.0))                                    # `center_crop`: Python's round, half to even
+
+
+def view_center(w: int, h: int, S: int) -> View:
+    """`load_image`'s geometry: Resize(S) -> CenterCrop(S)"""
+    rw, rh = _resized_size(w, h, S)
+    return View(0, 0, w, h, rw, rh, _centre(rw, S), _centre(rh, S), 0, S)
+
+
+def views_five(w: int, h: int, R: int, S: int) -> list:
+    """Resize(R) -> FiveCrop(S) in torchvision's order: top left, top right, bottom left, bottom right, centre"""
+    rw, rh = _resized_size(w, h, R)
+    if rw < S or rh < S:
+        raise ValueError(f"five-crop of {S} from a {w} x {h} image resized to {rw} x {rh}: the crop is larger than the image")
+    at = [(0, 0), (rw - S, 0), (0, rh - S), (rw - S, rh - S), (_centre(rw, S), _centre(rh, S))]
+    return [View(0, 0, w, h, rw, rh, left, top, 0, S) for left, top in at]
+
+
+def views_ten(w: int, h: int, R: int, S: int) -> list:
+    """Resize(R) -> TenCrop(S): the five crops, then the five crops of the MIRRORED resized image.  A window at `left` of the mirrored image
+    is the mirror image of the window at rw - S - left: view 5 is the mirrored top-right window, and so on."""
+    five = views_five(w, h, R, S)
+    return five + [v._replace(left=v.rw - S - v.left, flip=1) for v in five]
+
+
+def view_resized_crop(w: int, h: int, box, S: int, flip: bool = False) -> View:
+    """torchvision's resized_crop (what RandomResizedCrop applies once it has drawn `box` = (x0, y0, bw, bh)): the box becomes S x S,
+    each axis by its own ratio; `flip`: followed by hflip"""
+    x0, y0, bw, bh = (int(v) for v in box)
+    if bw < 1 or bh < 1 or x0 < 0 or y0 < 0 or x0 + bw > w or y0 + bh > h:
+        raise ValueError(f"box {tuple(box)} is empty or outside the {w} x {h} image")
+    return View(x0, y0, bw, bh, S, S, 0, 0, int(bool(flip)), S)
+
+
+def mirrored(views) -> list:
+    """the views and then the mirror image of each"""
+    views = list(views)
+    return views + [v._replace(flip=1 - v.flip) for v in views]
+
+
+def apply_view_pil(img, view, to_tensor: bool = True):
+    """the host route of one view with live Pillow; `img`: a PIL image or a uint8 [H, W, 3] array.  -> NormalizeToTensor's [3, size, size]
+    fp32 tensor, or with to_tensor=False the PIL image itself"""
+    v = View(*view)
+    S = v.size
+    im = img if isinstance(img, Image.Image) else Image.fromarray(np.asarray(img))
+    im = im.crop((v.x0, v.y0, v.x0 + v.bw, v.y0 + v.bh))
+    if (v.rw, v.rh) != (v.bw, v.bh):
+        im = im.resize((v.rw, v.rh), Image.BILINEAR)
+    im = im.crop((v.left, v.top, v.left + S, v.top + S))
+    if v.flip:
+        im = im.transpose(Image.FLIP_LEFT_RIGHT)
+    return NormalizeToTensor()(im) if to_tensor else im
+
+
+def view_rows(views_per_source, size: int) -> np.ndarray:
+    """one list of views per source -> the int64 [sum of views, 10] table of ops.image_views (source index, x0, y0, bw, bh, rw, rh, left, top,
+    flip), in source order and then view order; every view must be a `size` one"""
+    rows = []
+    for n, vs in enumerate(views_per_source):
+        for v in vs:
+            v = View(*v)
+            if v.size != size:
+                raise ValueError(f"a view of size {v.size} in a batch of size {size}")
+            rows.append((n,) + tuple(int(x) for x in v[:9]))
+    return np.array(rows, dtype=np.int64).reshape(len(rows), 10)
 
 
 def save_image(img: torch.Tensor, path: str) -> None:
@@ -72,7 +166,7 @@ def _decode(item) -> np.ndarray:
 
 
 class _Staged:
-    __slots__ = ("slot", "table", "nbytes", "t_decode", "t_pack")
+    __slots__ = ("slot", "table", "rows", "nbytes", "t_decode", "t_pack")
 
 
 class DeviceLoader:
@@ -81,6 +175,9 @@ class DeviceLoader:
     host, on at most MAX_DECODE_WORKERS threads; the pixels are packed into a reused pinned staging buffer together with their
     (offset, width, height) table, cross in one asynchronous copy, and one call of ops.image_resize_crop_norm does the rest.
     `batches()` keeps two staging slots so that the host work of batch i + 1 overlaps the copy and the kernels of batch i.
+    `views=fn` (load and batches): fn(width, height) -> a list of `View`s of this loader's size (views_five, views_ten, view_resized_crop, ...);
+    the output is then [sum of views, 3, size, size], in item order and then view order, through ops.image_views -- every source still crosses
+    once.  views=None is the centre crop through ops.image_resize_crop_norm.
     `load()` stages into slot 0: do not call it while a `batches()` iteration of the SAME loader is under way (it would overwrite a
     staged batch).  Owns two thread pools: `close()` it, use it as a context manager, or let the finaliser do it."""
 
@@ -114,17 +211,22 @@ class DeviceLoader:
         except Exception:                                                       # interpreter shutdown / half-built object
             pass
 
-    def _stage(self, items, slot: int) -> _Staged:
+    def _stage(self, items, slot: int, views=None) -> _Staged:
         t0 = time.perf_counter()
         arrays = list(self._pool.map(_decode, items)) if self.workers > 1 and len(items) > 1 else [_decode(i) for i in items]
         t1 = time.perf_counter()
         B = len(arrays)
-        head = (B * 24 + 63) // 64 * 64                                        # the table travels in front of the pixels
         table = np.empty((B, 3), dtype=np.int64)
         at = 0
         for b, a in enumerate(arrays):
             table[b] = (at, a.shape[1], a.shape[0])
             at += (a.size + 15) // 16 * 16
+        rows = None
+        if views is not None:
+            from . import ops
+            rows = ops.image_view_rows(table, view_rows([views(a.shape[1], a.shape[0]) for a in arrays], self.size))     # built once; _launch hands them on
+        front = table if rows is None else rows                                 # the table the kernels read travels in front of the pixels
+        head = (front.size * 8 + 63) // 64 * 64
         need = head + at
         if self._pinned[slot] is None or self._pinned[slot].numel() < need:
             cap = max(need, 1 << 20) * 5 // 4
@@ -133,19 +235,19 @@ class DeviceLoader:
         elif self._copied[slot] is not None:
             self._copied[slot].synchronize()                                   # the copy that last read this slot
         host = self._pinned[slot].numpy()
-        host[:B * 24] = table.reshape(-1).view(np.uint8)
+        host[:front.size * 8] = front.reshape(-1).view(np.uint8)
         for b, a in enumerate(arrays):
             o = head + int(table[b, 0])
             host[o:o + a.size] = a.reshape(-1)
         st = _Staged()
-        st.slot, st.table, st.nbytes, st.t_decode, st.t_pack = slot, table, need, t1 - t0, time.perf_counter() - t1
+        st.slot, st.table, st.rows, st.nbytes, st.t_decode, st.t_pack = slot, table, rows, need, t1 - t0, time.perf_counter() - t1
         return st
 
     def _launch(self, st: _Staged) -> torch.Tensor:
         from . import ops
         s = st.slot
-        B = st.table.shape[0]
-        head = (B * 24 + 63) // 64 * 64
+        front = st.table if st.rows is None else st.rows
+        head = (front.size * 8 + 63) // 64 * 64
         with torch.cuda.device(self.device):
             if self._dev[s] is None or self._dev[s].numel() < self._pinned[s].numel():
                 self._dev[s] = torch.empty(self._pinned[s].numel(), dtype=torch.uint8, device=self.device)
@@ -156,8 +258,11 @@ class DeviceLoader:
             ev = torch.cuda.Event(enable_timing=self.timing)
             ev.record()
             self._copied[s] = ev
-            out = ops.image_resize_crop_norm(self._dev[s][head:st.nbytes], st.table, self.size, dtype=self.dtype,
-                                             table_dev=self._dev[s][:B * 24].view(torch.int64))
+            front_dev = self._dev[s][:front.size * 8].view(torch.int64)
+            if st.rows is None:
+                out = ops.image_resize_crop_norm(self._dev[s][head:st.nbytes], st.table, self.size, dtype=self.dtype, table_dev=front_dev)
+            else:
+                out = ops.image_views(self._dev[s][head:st.nbytes], None, None, self.size, dtype=self.dtype, rows=st.rows, rows_dev=front_dev)
             if self.timing:
                 e2 = torch.cuda.Event(enable_timing=True)
                 e2.record()
@@ -165,17 +270,17 @@ class DeviceLoader:
         self.last_times = {"decode_s": st.t_decode, "pack_s": st.t_pack, "bytes": int(st.nbytes)}
         return out
 
-    def load(self, items) -> torch.Tensor:
+    def load(self, items, views=None) -> torch.Tensor:
         """one batch, synchronous on the host side (the GPU work is queued on the current stream)"""
-        return self._launch(self._stage(list(items), 0))
+        return self._launch(self._stage(list(items), 0, views))
 
-    def batches(self, items: Sequence, batch: int) -> Iterator[torch.Tensor]:
+    def batches(self, items: Sequence, batch: int, views=None) -> Iterator[torch.Tensor]:
         """consecutive batches of `batch` items; while the caller works on batch i, batch i + 1 is decoded and packed into the other slot"""
         items = list(items)
         chunks = [items[i:i + batch] for i in range(0, len(items), batch)]
-        fut = self._stager.submit(self._stage, chunks[0], 0) if chunks else None
+        fut = self._stager.submit(self._stage, chunks[0], 0, views) if chunks else None
         for i in range(len(chunks)):
             st = fut.result()
             if i + 1 < len(chunks):
-                fut = self._stager.submit(self._stage, chunks[i + 1], (i + 1) & 1)
+                fut = self._stager.submit(self._stage, chunks[i + 1], (i + 1) & 1, views)
             yield self._launch(st)

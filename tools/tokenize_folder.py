@@ -7,7 +7,12 @@ GPU (csrc/image_io.hip, the reference's PIL arithmetic bit for bit) -> `encoding
 Every rank writes <out>.rank<r>.npy (int64 [n, K], what the reference script saves; --uint16 for the compact wire format) and rank 0 prints
 ONE JSON line: images/s and where the time went (host decode, pack, H2D copy, resize kernels, encode).  --topk k also writes
 <out>.rank<r>.topk.npz (`ids` uint16 [n, K, k]: the k best codes of every token, best first; `scores` fp32 [n, K, k]: their exact cosine scores)
-and, for k >= 2, adds the near-tie census of the top-1 / top-2 margins to the JSON line; the .npy is the same bytes with and without it."""
+and, for k >= 2, adds the near-tie census of the top-1 / top-2 margins to the JSON line; the .npy is the same bytes with and without it.
+
+Augmented runs: --crops five | ten takes torchvision's FiveCrop / TenCrop(data_size) of the image resized to --resize R (shorter side, default
+data_size), --flip adds the mirror image of every view; each view is the tensor torchvision gives on the PIL image, bit for bit
+(csrc/image_views.hip, every file still crosses to the GPU once).  With more than one view per image the id file is int64 [n, views, K] (and the
+top-k arrays [n, views, K, k]), views in torchvision's order, and the JSON line names the recipe; --batch counts images, not views."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -31,10 +36,23 @@ ap.add_argument("--encoder-mode", default=None, choices=["exact", "fast"])
 ap.add_argument("--vae-mode", default=None, choices=["exact", "parity", "fast", "miopen"])
 ap.add_argument("--uint16", action="store_true", help="write tokens.to_uint16 ids instead of the reference's int64")
 ap.add_argument("--topk", type=int, default=0, help="k in 1..8: also keep every token's k best codes and their scores (SelftokPipeline.encoding_topk); the margin census needs k >= 2")
+ap.add_argument("--crops", default="center", choices=["center", "five", "ten"], help="views per image: the centre crop, FiveCrop or TenCrop of the resized image")
+ap.add_argument("--resize", type=int, default=0, help="R >= data_size: shorter side of the resize before the crops (default: data_size)")
+ap.add_argument("--flip", action="store_true", help="also emit the mirror image of every view")
 ap.add_argument("--out", default=None, help="prefix of the id files; nothing is written without it")
 a = ap.parse_args()
 if not 0 <= a.topk <= 8:
     ap.error("--topk k: 1 <= k <= 8")
+R = a.resize or a.data_size
+if R < a.data_size:
+    ap.error(f"--resize {R}: must be >= --data_size {a.data_size}")
+views, nviews = None, 1                # None: the centre crop of Resize(data_size), the route without views
+if a.crops != "center" or a.flip or R != a.data_size:
+    S = a.data_size
+    base = {"center": lambda w, h: [preprocess.views_five(w, h, R, S)[4]], "five": lambda w, h: preprocess.views_five(w, h, R, S),
+            "ten": lambda w, h: preprocess.views_ten(w, h, R, S)}[a.crops]
+    views = (lambda w, h: preprocess.mirrored(base(w, h))) if a.flip else base
+    nviews = {"center": 1, "five": 5, "ten": 10}[a.crops] * (2 if a.flip else 1)
 
 rank, world, local = D.init_from_env()
 torch.cuda.set_device(local)
@@ -65,7 +83,7 @@ topk_ids, topk_scores = [], []
 ids, split, marks = [], {"host_decode_s": 0.0, "pack_s": 0.0, "h2d_ms": 0.0, "resize_kernels_ms": 0.0, "encode_ms": 0.0}, []
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-for batch in loader.batches(items, a.batch):
+for batch in (loader.batches(items, a.batch, views=views) if views else loader.batches(items, a.batch)):
     ev, lt = loader.last_events, loader.last_times
     e3 = torch.cuda.Event(enable_timing=True)
     if a.topk:
@@ -85,6 +103,8 @@ for e0, e1, e2, e3 in marks:
     split["h2d_ms"] += e0.elapsed_time(e1); split["resize_kernels_ms"] += e1.elapsed_time(e2); split["encode_ms"] += e2.elapsed_time(e3)
 loader.close()
 ids = np.concatenate(ids) if ids else np.zeros((0, K), np.int64)
+if nviews > 1:
+    ids = ids.reshape(-1, nviews, K)
 if a.out:
     f = f"{a.out}.rank{rank}.npy"
     np.save(f, tokens.to_uint16(ids)) if a.uint16 else tokens.save_reference_npy(f, ids)
@@ -92,6 +112,8 @@ extra = {}
 if a.topk:
     topk_ids = np.concatenate(topk_ids) if topk_ids else np.zeros((0, K, a.topk), np.int64)
     topk_scores = np.concatenate(topk_scores) if topk_scores else np.zeros((0, K, a.topk), np.float32)
+    if nviews > 1:
+        topk_ids, topk_scores = topk_ids.reshape(-1, nviews, K, a.topk), topk_scores.reshape(-1, nviews, K, a.topk)
     if a.out:
         np.savez(f"{a.out}.rank{rank}.topk.npz", ids=tokens.to_uint16(topk_ids), scores=topk_scores)
     extra = {"topk": a.topk}
@@ -99,6 +121,9 @@ if a.topk:
         m = tokens.margins(topk_scores)
         extra.update({"rank0_margin_below_1e-5": int((m < 1e-5).sum()), "rank0_margin_below_1e-4": int((m < 1e-4).sum()),
                       "rank0_min_margin": float(m.min()) if m.size else None})
+if views:
+    extra.update({"crops": a.crops, "resize": R, "flip": bool(a.flip), "views_per_image": nviews, "views": n * nviews,
+                  "recipe": f"Resize({R}) -> {dict(center='CenterCrop', five='FiveCrop', ten='TenCrop')[a.crops]}({a.data_size})" + (" + mirror images" if a.flip else "")})
 slowest = D.max_over_ranks(wall, dev)
 D.barrier()
 if rank == 0:
