@@ -5,7 +5,7 @@
 //   below says it again for this file): horizontal pass of the five maps x, y, x*x, y*y, x*y (taps ascending), vertical pass (taps
 //   ascending), the SSIM quotient, the fp64 sum over channels and windows.
 //   MSE with evaluate.psnr_each's operations: d = float32(recon) - o and d * d in fp32, summed in fp64.
-//   `quantize`: both inputs first become the bytes save_image writes (to_u8_one below, the copy of csrc/image_io.hip's), x = byte / 255.0
+//   `quantize`: both inputs first become the bytes save_image writes (to_u8_one of csrc/u8_shared.h), x = byte / 255.0
 //   in fp64, and the squared error is the exact integer sum of (bx - by)^2.
 // One workgroup = one 32 x 16 tile of windows of one (image, channel) plane: the tile's 42 x 26 pixels of x and y go to LDS as fp64 (source
 // addresses clamped to the plane, so nothing outside the two tensors is read), the horizontal pass writes five 26 x 32 fp64 maps to LDS,
@@ -15,6 +15,7 @@
 // image alone.  LDS: 2 * 26 * 42 * 8 + 5 * 26 * 32 * 8 = 50752 bytes (three workgroups per CU, as many as fp32 inputs would give).
 #include "common.h"
 #include "selftok_hip_ext.h"
+#include "u8_shared.h"
 #include <stdio.h>
 
 #pragma clang fp contract(off)
@@ -33,27 +34,6 @@ struct Args {
     int H, W, ntx, nty, orig_signed, quantize;
     double g[KW];
 };
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ float round_bf16(float f)              // fp32 -> nearest bf16 (ties to even), as fp32; not for NaN
-{
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return __uint_as_float(u & 0xFFFF0000u);
-}
-
-// csrc/image_io.hip's to_u8_one, copied: both are pinned to tests/image_io_cases.py::to_u8_bf16 / to_u8_f32
-template <bool BF16>
-__device__ __forceinline__ unsigned char to_u8_one(float x)
-{
-    if (x != x) return 0;                                         // NaN: this project's choice
-    float y = x * 255.0f;
-    if (BF16) y = round_bf16(y);
-    y = y + 0.5f;
-    if (BF16) y = round_bf16(y);
-    y = y < 0.0f ? 0.0f : (y > 255.0f ? 255.0f : y);
-    return (unsigned char)(int)y;
-}
 
 // grid: B * 3 * nty * ntx workgroups, tile column fastest; ws[2 * workgroup + {0: sum of the tile's SSIM values, 1: sum of its pixels' squared errors}]
 template <bool RB, bool OB>

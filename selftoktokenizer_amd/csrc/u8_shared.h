@@ -1,4 +1,5 @@
-// The byte `save_image` writes for a [0, 1] value, and the bf16 helpers it needs: shared by the input stages of csrc/lpips.hip and csrc/fid.hip.
+// The byte `save_image` writes for a [0, 1] value, and the bf16 helpers it needs.  The only definition: csrc/image_io.hip (img_to_u8), csrc/image_metrics.hip
+// and the input stages of csrc/lpips.hip and csrc/fid.hip all include it.
 #pragma once
 #include "common.h"
 
@@ -12,11 +13,11 @@ __device__ __forceinline__ float round_bf16(float f)              // fp32 -> nea
     return __uint_as_float(u & 0xFFFF0000u);
 }
 
-// csrc/image_io.hip's to_u8_one, copied (as csrc/image_metrics.hip does): pinned to tests/image_io_cases.py::to_u8_bf16 / to_u8_f32
+// pinned to tests/image_io_cases.py::to_u8_bf16 / to_u8_f32: x * 255, + 0.5, each rounded to the tensor's type, clamp, truncate
 template <bool BF16>
 __device__ __forceinline__ unsigned char to_u8_one(float x)
 {
-    if (x != x) return 0;
+    if (x != x) return 0;                                         // NaN: this project's choice
     float y = x * 255.0f;
     if (BF16) y = round_bf16(y);
     y = y + 0.5f;

@@ -1096,7 +1096,7 @@ def ex_attention(q: torch.Tensor, k1, v1, heads: int, k2=None, v2=None, slots1: 
     return out
 
 
-# ---- device image I/O (csrc/image_io.hip, include/selftok_hip_ext.h) ----
+# ---- device image I/O (csrc/image_io.hip, csrc/image_views.hip, include/selftok_hip_ext.h) ----
 _IMG_LUT = {}
 
 
@@ -1120,46 +1120,53 @@ def _img_table(table):
     return t
 
 
+def _image_resample(fn, entry, layout, dev_name, packed, t, size, dtype, out, t_dev, return_tables, empty_ok=False):
+    """the body image_resize_crop_norm and image_views share: `t` the host table [N, cols] of the C entry `entry`, `layout` its tap-row query,
+    `fn` / `dev_name` the public function and its device-table argument for the messages; `empty_ok`: N = 0 gives an empty tensor"""
+    import numpy as np
+    _need_cuda(packed, out, t_dev)
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise _lib.SelftokHipError(f"{fn}: `packed` must be a contiguous 1-D uint8 tensor, got {packed.dtype} {tuple(packed.shape)}")
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.SelftokHipError(f"{fn}: output dtype {dtype}: expected bfloat16 or float32")
+    (N, cols), S = t.shape, int(size)
+    if out is None:
+        out = torch.empty(N, 3, max(S, 0), max(S, 0), dtype=dtype, device=packed.device)
+    elif out.dtype != dtype or tuple(out.shape) != (N, 3, S, S) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"{fn}: `out` must be a contiguous {dtype} [{N}, 3, {S}, {S}] tensor")
+    if N == 0 and empty_ok:
+        return (out, {}) if return_tables else out
+    lib = _lib.load()
+    nbytes = getattr(lib, entry + "_workspace_bytes")(t.ctypes.data, N, S)
+    if nbytes == 0:
+        _lib.check(-1, entry + "_workspace_bytes")
+    if t_dev is None:
+        t_dev = torch.from_numpy(t).to(packed.device)
+    elif t_dev.dtype != torch.int64 or t_dev.numel() != cols * N or not t_dev.is_contiguous():
+        raise _lib.SelftokHipError(f"{fn}: `{dev_name}` must be the contiguous int64 [{'B' if cols == 3 else 'V'}, {cols}] table")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
+    lut = image_norm_lut(packed.device, dtype)
+    _lib.check(getattr(lib, entry)(_p(packed), packed.numel(), t.ctypes.data, _p(t_dev), N, S, _p(out), int(dtype == torch.bfloat16), _p(lut), _p(ws), nbytes, _stream()), entry)
+    if not return_tables:
+        return out
+    lay = np.zeros(4, dtype=np.int64)
+    _lib.check(getattr(lib, layout)(t.ctypes.data, N, S, lay.ctypes.data), layout)
+    wi = ws[:(nbytes // 4) * 4].view(torch.int32).cpu().numpy()
+    tabs = {}
+    for name, base, ks in (("h", int(lay[0]), int(lay[1])), ("v", int(lay[2]), int(lay[3]))):
+        rows = wi[base:base + N * S * ks].reshape(N, S, ks)
+        tabs[name] = (rows[:, :, 0].copy(), rows[:, :, 1].copy(), rows[:, :, 2:].copy())
+    return out, tabs
+
+
 def image_resize_crop_norm(packed: torch.Tensor, table, size: int, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None,
                            table_dev: Optional[torch.Tensor] = None, return_tables: bool = False):
     """B RGB uint8 HWC images of any sizes, packed in the 1-D uint8 device tensor `packed`; `table` [B, 3] on the host: byte offset, width,
     height of each.  -> [B, 3, size, size] in [-1, 1], bf16 or fp32: NormalizeToTensor(CenterCrop(size)(Resize(size)(PIL image))) bit for bit.
     `table_dev`: the same table already on the device (int64), else it is copied here.  `out`: write into this contiguous tensor.
     return_tables: also the integer tap rows the kernels used, {'h' | 'v': (first [B, size], n [B, size], k [B, size, kmax])} (tests)."""
-    import numpy as np
-    _need_cuda(packed, out, table_dev)
-    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
-        raise _lib.SelftokHipError(f"image_resize_crop_norm: `packed` must be a contiguous 1-D uint8 tensor, got {packed.dtype} {tuple(packed.shape)}")
-    if dtype not in (torch.bfloat16, torch.float32):
-        raise _lib.SelftokHipError(f"image_resize_crop_norm: output dtype {dtype}: expected bfloat16 or float32")
-    t = _img_table(table)
-    B, S = t.shape[0], int(size)
-    lib = _lib.load()
-    nbytes = lib.selftok_img_resize_crop_norm_u8_workspace_bytes(t.ctypes.data, B, S)
-    if nbytes == 0:
-        _lib.check(-1, "selftok_img_resize_crop_norm_u8_workspace_bytes")
-    if table_dev is None:
-        table_dev = torch.from_numpy(t).to(packed.device)
-    elif table_dev.dtype != torch.int64 or table_dev.numel() != 3 * B or not table_dev.is_contiguous():
-        raise _lib.SelftokHipError("image_resize_crop_norm: `table_dev` must be the contiguous int64 [B, 3] table")
-    if out is None:
-        out = torch.empty(B, 3, S, S, dtype=dtype, device=packed.device)
-    elif out.dtype != dtype or tuple(out.shape) != (B, 3, S, S) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"image_resize_crop_norm: `out` must be a contiguous {dtype} [{B}, 3, {S}, {S}] tensor")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
-    lut = image_norm_lut(packed.device, dtype)
-    _lib.check(lib.selftok_img_resize_crop_norm_u8(_p(packed), packed.numel(), t.ctypes.data, _p(table_dev), B, S, _p(out), int(dtype == torch.bfloat16),
-                                                   _p(lut), _p(ws), nbytes, _stream()), "selftok_img_resize_crop_norm_u8")
-    if not return_tables:
-        return out
-    lay = np.zeros(4, dtype=np.int64)
-    _lib.check(lib.selftok_img_resize_tables_layout(t.ctypes.data, B, S, lay.ctypes.data), "selftok_img_resize_tables_layout")
-    wi = ws[:(nbytes // 4) * 4].view(torch.int32).cpu().numpy()
-    tabs = {}
-    for name, base, ks in (("h", int(lay[0]), int(lay[1])), ("v", int(lay[2]), int(lay[3]))):
-        rows = wi[base:base + B * S * ks].reshape(B, S, ks)
-        tabs[name] = (rows[:, :, 0].copy(), rows[:, :, 1].copy(), rows[:, :, 2:].copy())
-    return out, tabs
+    return _image_resample("image_resize_crop_norm", "selftok_img_resize_crop_norm_u8", "selftok_img_resize_tables_layout", "table_dev",
+                           packed, _img_table(table), size, dtype, out, table_dev, return_tables)
 
 
 def image_view_rows(sources_table, views):
@@ -1185,46 +1192,12 @@ def image_views(packed: torch.Tensor, sources_table, views, size: int, dtype=tor
     `sources_table` / `views` are not read (pass None).  `rows_dev`: the same rows already on the device (int64 [V, 12]), else they are copied
     here.  `out`: write into this contiguous tensor.  return_tables: also the integer tap rows, {'h' | 'v': (first [V, size], n [V, size], k [V, size, kmax])} (tests)."""
     import numpy as np
-    _need_cuda(packed, out, rows_dev)
-    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
-        raise _lib.SelftokHipError(f"image_views: `packed` must be a contiguous 1-D uint8 tensor, got {packed.dtype} {tuple(packed.shape)}")
-    if dtype not in (torch.bfloat16, torch.float32):
-        raise _lib.SelftokHipError(f"image_views: output dtype {dtype}: expected bfloat16 or float32")
     if rows is None:
-        t = image_view_rows(sources_table, views)
-    else:
-        t = rows
-        if not isinstance(t, np.ndarray) or t.dtype != np.int64 or t.ndim != 2 or t.shape[1] != 12 or not t.flags["C_CONTIGUOUS"]:
-            raise _lib.SelftokHipError("image_views: `rows` must be the contiguous int64 numpy [V, 12] table of image_view_rows")
-    V, S = t.shape[0], int(size)
-    if out is None:
-        out = torch.empty(V, 3, max(S, 0), max(S, 0), dtype=dtype, device=packed.device)
-    elif out.dtype != dtype or tuple(out.shape) != (V, 3, S, S) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"image_views: `out` must be a contiguous {dtype} [{V}, 3, {S}, {S}] tensor")
-    if V == 0:
-        return (out, {}) if return_tables else out
-    lib = _lib.load()
-    nbytes = lib.selftok_img_views_u8_workspace_bytes(t.ctypes.data, V, S)
-    if nbytes == 0:
-        _lib.check(-1, "selftok_img_views_u8_workspace_bytes")
-    if rows_dev is None:
-        rows_dev = torch.from_numpy(t).to(packed.device)
-    elif rows_dev.dtype != torch.int64 or rows_dev.numel() != 12 * V or not rows_dev.is_contiguous():
-        raise _lib.SelftokHipError("image_views: `rows_dev` must be the contiguous int64 [V, 12] table")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
-    lut = image_norm_lut(packed.device, dtype)
-    _lib.check(lib.selftok_img_views_u8(_p(packed), packed.numel(), t.ctypes.data, _p(rows_dev), V, S, _p(out), int(dtype == torch.bfloat16),
-                                        _p(lut), _p(ws), nbytes, _stream()), "selftok_img_views_u8")
-    if not return_tables:
-        return out
-    lay = np.zeros(4, dtype=np.int64)
-    _lib.check(lib.selftok_img_views_tables_layout(t.ctypes.data, V, S, lay.ctypes.data), "selftok_img_views_tables_layout")
-    wi = ws[:(nbytes // 4) * 4].view(torch.int32).cpu().numpy()
-    tabs = {}
-    for name, base, ks in (("h", int(lay[0]), int(lay[1])), ("v", int(lay[2]), int(lay[3]))):
-        rows = wi[base:base + V * S * ks].reshape(V, S, ks)
-        tabs[name] = (rows[:, :, 0].copy(), rows[:, :, 1].copy(), rows[:, :, 2:].copy())
-    return out, tabs
+        rows = image_view_rows(sources_table, views)
+    elif not isinstance(rows, np.ndarray) or rows.dtype != np.int64 or rows.ndim != 2 or rows.shape[1] != 12 or not rows.flags["C_CONTIGUOUS"]:
+        raise _lib.SelftokHipError("image_views: `rows` must be the contiguous int64 numpy [V, 12] table of image_view_rows")
+    return _image_resample("image_views", "selftok_img_views_u8", "selftok_img_views_tables_layout", "rows_dev", packed, rows, size, dtype, out, rows_dev, return_tables,
+                           empty_ok=True)
 
 
 def image_to_u8(img: torch.Tensor) -> torch.Tensor:

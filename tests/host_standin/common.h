@@ -1,5 +1,6 @@
-// Host stand-in for csrc/common.h + the HIP runtime, used by tests/test_image_io_standin_cpu.py ONLY: csrc/image_io.hip is plain C++ around its
-// launches, so with these few definitions a host compiler builds it and every "kernel" runs as nested loops over the grid.  The arithmetic
+// Host stand-in for csrc/common.h + the HIP runtime, used by tests/test_image_io_standin_cpu.py and tests/test_image_views_standin_cpu.py: csrc/image_io.hip,
+// csrc/image_views.hip and the headers they include (image_resample_shared.h, u8_shared.h; the tests copy them beside this file) are plain C++ around their
+// launches, so with these few definitions a host compiler builds them and every "kernel" runs as nested loops over the grid.  The arithmetic
 // (fp64 tap weights, integer sums, the bf16 rounding) is then the host's IEEE arithmetic -- the same operations the GPU executes.
 #pragma once
 #include <stdint.h>

@@ -120,6 +120,59 @@ def test_mixed_batch_order_and_sentinels(golden):
     assert torch.equal(bigf[1:B + 1].to(torch.bfloat16), mixed) and bool((bigf[0] == -7.0).all()) and bool((bigf[B + 1] == -7.0).all())
 
 
+TINY = [IO.Case("tiny_wide", 40, 24, 16, "noise"), IO.Case("tiny_high", 24, 40, 16, "noise"), IO.Case("tiny_identity", 16, 16, 16, "noise"),
+        IO.Case("tiny_taps", 37, 180, 16, "noise")]                                         # wider, higher, identity taps on both axes, many vertical taps
+
+
+@pytest.fixture(scope="module")
+def tiny():
+    """the four tiny sources packed, their [4, 3] table, and the emulation's tensors {dtype: device [4, 3, 16, 16]}, computed once"""
+    buf, table = pack([IO.image(c) for c in TINY])
+    u8 = [IO.resize_crop(IO.image(c), 16) for c in TINY]
+    want = {torch.bfloat16: torch.from_numpy(np.stack([IO.to_tensor(u, True) for u in u8]).view(np.int16)).view(torch.bfloat16).to(DEV),
+            torch.float32: torch.from_numpy(np.stack([IO.to_tensor(u, False) for u in u8])).to(DEV)}
+    return buf, table, want
+
+
+def test_tiny_batch_guard_bands_and_sentinels(tiny):
+    """the workspace inside a larger buffer of 0xC3 bytes, the output between two sentinel planes: nothing outside the queried size and
+    outside the batch is written, and the batch equals the emulation"""
+    buf, table, want = tiny
+    B, guard = len(TINY), 4096
+    lib = _lib.load()
+    n = lib.selftok_img_resize_crop_norm_u8_workspace_bytes(table.ctypes.data, B, 16)
+    assert n > 0
+    table_dev = torch.from_numpy(table).to(DEV)
+    for dtype in (torch.bfloat16, torch.float32):
+        wsbuf = torch.full((guard + n + guard,), 0xC3, dtype=torch.uint8, device=DEV)
+        big = torch.full((B + 2, 3, 16, 16), -7.0, dtype=dtype, device=DEV)
+        lut = ops.image_norm_lut(DEV, dtype)
+        assert wsbuf.data_ptr() % 16 == 0
+        rc = lib.selftok_img_resize_crop_norm_u8(buf.data_ptr(), buf.numel(), table.ctypes.data, table_dev.data_ptr(), B, 16, big[1:].data_ptr(), int(dtype == torch.bfloat16),
+                                                 lut.data_ptr(), wsbuf.data_ptr() + guard, n, torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, lib.selftok_last_error()
+        assert np.array_equal(bits(big[1:B + 1]), bits(want[dtype])) and bool((big[0] == -7.0).all()) and bool((big[B + 1] == -7.0).all())
+        assert bool((wsbuf[:guard] == 0xC3).all()) and bool((wsbuf[guard + n:] == 0xC3).all())
+        assert np.array_equal(bits(ops.image_resize_crop_norm(buf, table, 16, dtype=dtype)), bits(want[dtype]))
+
+
+def test_tiny_batch_with_a_device_table_that_disagrees(tiny):
+    """device rows that disagree with the host copy are skipped, the others stay correct, the call returns 0"""
+    buf, table, want = tiny
+    bad = table.copy()
+    bad[0] = (0, 64, 64)                                                                     # inside the buffer, but 64 rows -> 16 needs more vertical taps than the host sized
+    bad[1, 0] = buf.numel()                                                                  # an offset past the packed buffer
+    assert 3 * 64 * 64 <= buf.numel()
+    lib = _lib.load()
+    lay, lay0 = np.zeros(4, dtype=np.int64), np.zeros(4, dtype=np.int64)
+    alone = np.ascontiguousarray(bad[0:1])
+    assert lib.selftok_img_resize_tables_layout(table.ctypes.data, 4, 16, lay.ctypes.data) == 0 and lib.selftok_img_resize_tables_layout(alone.ctypes.data, 1, 16, lay0.ctypes.data) == 0
+    assert lay0[3] > lay[3]
+    for dtype in (torch.bfloat16, torch.float32):
+        out = ops.image_resize_crop_norm(buf, table, 16, dtype=dtype, out=torch.full((4, 3, 16, 16), -7.0, dtype=dtype, device=DEV), table_dev=torch.from_numpy(bad).to(DEV))
+        assert bool((out[:2] == -7.0).all()) and np.array_equal(bits(out[2:]), bits(want[dtype][2:]))
+
+
 def test_batch_of_256(golden):
     small = [c for c in IO.MIXED if c.w * c.h <= 1 << 20]
     cases = [small[b % len(small)] for b in range(256)]

@@ -23,6 +23,8 @@ def lib(tmp_path_factory):
     d = tmp_path_factory.mktemp("standin")
     shutil.copy(os.path.join(ROOT, "tests", "host_standin", "common.h"), d / "common.h")
     shutil.copy(os.path.join(ROOT, "selftoktokenizer_amd", "csrc", "image_io.hip"), d / "image_io.inc")
+    for h in ("image_resample_shared.h", "u8_shared.h"):                    # the headers the file includes, beside it
+        shutil.copy(os.path.join(ROOT, "selftoktokenizer_amd", "csrc", h), d / h)
     (d / "selftok_hip_ext.h").write_text("#pragma once\n")
     (d / "unit.cpp").write_text('#include "common.h"\nextern "C" {\n'
                                 "size_t selftok_img_resize_crop_norm_u8_workspace_bytes(const long*, int, int);\n"

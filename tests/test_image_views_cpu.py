@@ -136,8 +136,9 @@ def test_image_views_compiles_for_gfx950_without_scratch(tmp_path):
     scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
     assert len(kernels) == 5 and len(scratch) == len(kernels), (kernels, scratch)                # plan, tables, horizontal, vertical x {bf16, fp32}
     assert all(s == 0 for s in scratch), dict(zip(kernels, scratch))
-    src = open(os.path.join(G.CSRC, "image_views.hip")).read()
-    assert "asm" not in src.replace("namespace", "") and "#pragma clang fp contract(off)" in src   # plain C++, every fp64 operation rounded on its own
+    src, shared = (open(os.path.join(G.CSRC, f)).read() for f in ("image_views.hip", "image_resample_shared.h"))
+    assert "asm" not in (src + shared).replace("namespace", "")               # plain C++, in the unit and in the resample it includes,
+    assert "#pragma clang fp contract(off)" in src and "#pragma clang fp contract(off)" in shared   # every fp64 operation rounded on its own
     assert "-ffp-contract=off" in cmd
 
 
