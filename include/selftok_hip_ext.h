@@ -83,6 +83,32 @@ int selftok_img_views_tables_layout(const long* views_host, int V, int S, long* 
 int selftok_img_views_u8(const unsigned char* packed, size_t packed_bytes, const long* views_host, const long* views_dev, int V, int S, void* out, int out_bf16,
                          const void* lut, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* ---- device image views with a chosen Pillow filter ------------------------------------------------------
+ * selftok_img_views_u8 with one more argument, `filter`, Pillow's own code: BILINEAR = 2, BICUBIC = 3 (a = -0.5, support 2), BOX = 4
+ * (1 on -0.5 < x <= 0.5, support 0.5).  The same [V, 12] rows, limits, host-table / device-table rule, lut, outputs and workspace layout;
+ * the tap rows are as wide as the filter needs, ksize = 2 * ceil(support * max(scale, 1)) + 1, and the query and the layout call take
+ * the filter too.  filter = 2 gives the bits and the tap rows of selftok_img_views_u8.  LANCZOS (1) and HAMMING (5) are refused by name:
+ * their weights are libm's sin / cos, whose bits the device does not promise; NEAREST (0) is refused too (Pillow does not resample it
+ * through coefficient tables).  SELFTOK_EINVAL, nothing launched. */
+size_t selftok_img_views_filter_u8_workspace_bytes(const long* views_host, int V, int S, int filter);
+int selftok_img_views_filter_tables_layout(const long* views_host, int V, int S, int filter, long* layout4);
+int selftok_img_views_filter_u8(const unsigned char* packed, size_t packed_bytes, const long* views_host, const long* views_dev, int V, int S, int filter, void* out,
+                                int out_bf16, const void* lut, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* ---- device whole-frame resize: Pillow's Image.resize((ow, oh), filter) on uint8 HWC frames ---------------
+ * N frames that lie in `packed` are resized into other regions of the SAME buffer (the BOX halvings of the ADM centre crop are chains of
+ * such calls).  One row of six longs per frame: source byte offset, W, H, destination byte offset, ow, oh; the table is passed twice,
+ * under the rule of the entries above.  Per frame, bit for bit: horizontal pass first, uint8 between the passes, an axis whose length does
+ * not change is not resampled, fp64 weights, 22-bit coefficients, (2^21 + sum) >> 22, clip.  `filter` as above.
+ * The host copy is validated (SELFTOK_EINVAL with a message, nothing launched): 1 <= N <= 65535, 1 <= W, H, ow, oh <= 65536, every
+ * source and destination region inside packed_bytes, no destination region overlapping any source or destination region of the call
+ * (sources may coincide).  The device re-checks ITS copy against the same rules and against what the host copy sized the launch and the
+ * workspace for; a frame that disagrees is skipped, its destination stays untouched, return 0.  The workspace (tap rows of every frame
+ * and its H x ow uint8 rows between the passes) is sized by the query, 0 with selftok_last_error set on a bad table; 16-byte aligned. */
+size_t selftok_img_resize_u8_workspace_bytes(const long* frames_host, int N, int filter);
+int selftok_img_resize_u8(unsigned char* packed, size_t packed_bytes, const long* frames_host, const long* frames_dev, int N, int filter, void* workspace,
+                          size_t workspace_bytes, hipStream_t stream);
+
 /* ---- device image output: [B, 3, H, W] in [0, 1] -> uint8 [B, H, W, 3] ---------------------------------
  * torchvision.utils.save_image's arithmetic in the tensor's own type: x * 255 rounded to the type, + 0.5 rounded to the type, clamp to
  * [0, 255], truncate.  in_bf16 != 0: bf16 input, else fp32.  +Inf -> 255, -Inf -> 0; NaN -> 0 (this project's choice: torch's

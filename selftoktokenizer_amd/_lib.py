@@ -91,6 +91,11 @@ EXT_SIGNATURES = {
     "selftok_img_views_u8_workspace_bytes": (_sz, [_vp, _i, _i]),
     "selftok_img_views_tables_layout": (_i, [_vp, _i, _i, _vp]),
     "selftok_img_views_u8": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "selftok_img_views_filter_u8_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "selftok_img_views_filter_tables_layout": (_i, [_vp, _i, _i, _i, _vp]),
+    "selftok_img_views_filter_u8": (_i, [_vp, _sz, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "selftok_img_resize_u8_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "selftok_img_resize_u8": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "selftok_img_to_u8": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
     "selftok_img_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "selftok_img_metrics": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),

@@ -159,15 +159,21 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     return out
 
 
-def folder_loader(paths: Sequence[str], size: int, device=None) -> Callable[[int, int], torch.Tensor]:
+def folder_loader(paths: Sequence[str], size: int, device=None, preprocess: str = "reference") -> Callable[[int, int], torch.Tensor]:
     """load_batch for `evaluate`.  Default: `preprocess.load_image` per file on the host.  With a `device` (extension): the files are only
     decoded on the host and the resize / crop / normalise runs on that GPU (preprocess.DeviceLoader) -- the same fp32 values, bit for bit,
-    already on the device (the PSNR is taken against them, so they stay fp32; `encoding` rounds to bf16 itself)."""
-    from . import preprocess
+    already on the device (the PSNR is taken against them, so they stay fp32; `encoding` rounds to bf16 itself).
+    preprocess: "reference" (load_image), "bicubic" (load_image(filter="bicubic")) or "adm" (load_image_adm), by either route."""
+    from . import preprocess as P
+    P._check_preprocess(preprocess)
     if device is not None:
-        loader = preprocess.DeviceLoader(size, device, dtype=torch.float32)
+        loader = P.DeviceLoader(size, device, dtype=torch.float32) if preprocess == "reference" else P.DeviceLoader(size, device, dtype=torch.float32, preprocess=preprocess)
         return lambda lo, hi: loader.load(paths[lo:hi])
 
     def load(lo: int, hi: int) -> torch.Tensor:
-        return torch.stack([preprocess.load_image(p, size) for p in paths[lo:hi]])
+        if preprocess == "adm":
+            return torch.stack([P.load_image_adm(p, size) for p in paths[lo:hi]])
+        if preprocess == "bicubic":
+            return torch.stack([P.load_image(p, size, filter="bicubic") for p in paths[lo:hi]])
+        return torch.stack([P.load_image(p, size) for p in paths[lo:hi]])
     return load

@@ -1120,9 +1120,29 @@ def _img_table(table):
     return t
 
 
-def _image_resample(fn, entry, layout, dev_name, packed, t, size, dtype, out, t_dev, return_tables, empty_ok=False):
+IMAGE_FILTERS = {"bilinear": 2, "bicubic": 3, "box": 4}                      # Pillow's own codes (PIL.Image.Resampling)
+_UNSERVED_FILTERS = {0: "NEAREST", 1: "LANCZOS", 5: "HAMMING", "nearest": "NEAREST", "lanczos": "LANCZOS", "hamming": "HAMMING"}
+
+
+def image_filter_code(filter, fn="image filter") -> int:
+    """a filter named as Pillow names it ('bilinear' / 'bicubic' / 'box', Image.BILINEAR / BICUBIC / BOX, 2 / 3 / 4) -> its code; LANCZOS,
+    HAMMING and NEAREST are refused by name, before the library is asked"""
+    key = filter.lower() if isinstance(filter, str) else int(filter)
+    if key in _UNSERVED_FILTERS:
+        name = _UNSERVED_FILTERS[key]
+        why = "Pillow does not resample it through coefficient tables" if name == "NEAREST" else "its weights are libm's sin / cos, whose bits the device does not promise"
+        raise _lib.SelftokHipError(f"{fn}: Pillow's {name} filter is not served on the device ({why}); BILINEAR, BICUBIC and BOX are")
+    if key in IMAGE_FILTERS:
+        return IMAGE_FILTERS[key]
+    if key in IMAGE_FILTERS.values():
+        return key
+    raise _lib.SelftokHipError(f"{fn}: unknown filter {filter!r}: expected one of {sorted(IMAGE_FILTERS)} or Pillow's codes 2, 3, 4")
+
+
+def _image_resample(fn, entry, layout, dev_name, packed, t, size, dtype, out, t_dev, return_tables, empty_ok=False, filter=None):
     """the body image_resize_crop_norm and image_views share: `t` the host table [N, cols] of the C entry `entry`, `layout` its tap-row query,
-    `fn` / `dev_name` the public function and its device-table argument for the messages; `empty_ok`: N = 0 gives an empty tensor"""
+    `fn` / `dev_name` the public function and its device-table argument for the messages; `empty_ok`: N = 0 gives an empty tensor; `filter`: the
+    code the entry, its query and its layout call take after S (the entries with a filter argument), None for the bilinear entries"""
     import numpy as np
     _need_cuda(packed, out, t_dev)
     if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
@@ -1137,7 +1157,8 @@ def _image_resample(fn, entry, layout, dev_name, packed, t, size, dtype, out, t_
     if N == 0 and empty_ok:
         return (out, {}) if return_tables else out
     lib = _lib.load()
-    nbytes = getattr(lib, entry + "_workspace_bytes")(t.ctypes.data, N, S)
+    fa = () if filter is None else (int(filter),)
+    nbytes = getattr(lib, entry + "_workspace_bytes")(t.ctypes.data, N, S, *fa)
     if nbytes == 0:
         _lib.check(-1, entry + "_workspace_bytes")
     if t_dev is None:
@@ -1146,11 +1167,11 @@ def _image_resample(fn, entry, layout, dev_name, packed, t, size, dtype, out, t_
         raise _lib.SelftokHipError(f"{fn}: `{dev_name}` must be the contiguous int64 [{'B' if cols == 3 else 'V'}, {cols}] table")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
     lut = image_norm_lut(packed.device, dtype)
-    _lib.check(getattr(lib, entry)(_p(packed), packed.numel(), t.ctypes.data, _p(t_dev), N, S, _p(out), int(dtype == torch.bfloat16), _p(lut), _p(ws), nbytes, _stream()), entry)
+    _lib.check(getattr(lib, entry)(_p(packed), packed.numel(), t.ctypes.data, _p(t_dev), N, S, *fa, _p(out), int(dtype == torch.bfloat16), _p(lut), _p(ws), nbytes, _stream()), entry)
     if not return_tables:
         return out
     lay = np.zeros(4, dtype=np.int64)
-    _lib.check(getattr(lib, layout)(t.ctypes.data, N, S, lay.ctypes.data), layout)
+    _lib.check(getattr(lib, layout)(t.ctypes.data, N, S, *fa, lay.ctypes.data), layout)
     wi = ws[:(nbytes // 4) * 4].view(torch.int32).cpu().numpy()
     tabs = {}
     for name, base, ks in (("h", int(lay[0]), int(lay[1])), ("v", int(lay[2]), int(lay[3]))):
@@ -1183,21 +1204,57 @@ def image_view_rows(sources_table, views):
 
 
 def image_views(packed: torch.Tensor, sources_table, views, size: int, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None,
-                rows_dev: Optional[torch.Tensor] = None, return_tables: bool = False, rows=None):
+                rows_dev: Optional[torch.Tensor] = None, return_tables: bool = False, rows=None, filter="bilinear"):
     """V views of RGB uint8 HWC sources packed in the 1-D uint8 device tensor `packed` -> [V, 3, size, size] in [-1, 1], bf16 or fp32: per view
     NormalizeToTensor(hflip?(crop(window)(resize(crop(box)(PIL image))))) bit for bit (preprocess.apply_view_pil; csrc/image_views.hip).
     `sources_table` [N, 3] on the host: byte offset, width, height of each source; `views` [V, 10] on the host: source index, x0, y0, bw, bh,
     rw, rh, left, top, flip (preprocess.view_rows).  Several views may name one source.  V = 0 gives an empty tensor.
     `rows`: image_view_rows(sources_table, views) already built on the host (contiguous int64 numpy [V, 12]); it is then the table of record and
     `sources_table` / `views` are not read (pass None).  `rows_dev`: the same rows already on the device (int64 [V, 12]), else they are copied
-    here.  `out`: write into this contiguous tensor.  return_tables: also the integer tap rows, {'h' | 'v': (first [V, size], n [V, size], k [V, size, kmax])} (tests)."""
+    here.  `out`: write into this contiguous tensor.  return_tables: also the integer tap rows, {'h' | 'v': (first [V, size], n [V, size], k [V, size, kmax])} (tests).
+    `filter`: 'bilinear' (the default: selftok_img_views_u8, as before), 'bicubic' or 'box', or Pillow's Image.BILINEAR / BICUBIC / BOX -- the
+    resample of every view then uses that filter (selftok_img_views_filter_u8, csrc/image_filters.hip); LANCZOS / HAMMING / NEAREST are refused."""
     import numpy as np
+    code = image_filter_code(filter, "image_views")
     if rows is None:
         rows = image_view_rows(sources_table, views)
     elif not isinstance(rows, np.ndarray) or rows.dtype != np.int64 or rows.ndim != 2 or rows.shape[1] != 12 or not rows.flags["C_CONTIGUOUS"]:
         raise _lib.SelftokHipError("image_views: `rows` must be the contiguous int64 numpy [V, 12] table of image_view_rows")
-    return _image_resample("image_views", "selftok_img_views_u8", "selftok_img_views_tables_layout", "rows_dev", packed, rows, size, dtype, out, rows_dev, return_tables,
-                           empty_ok=True)
+    if code == IMAGE_FILTERS["bilinear"]:
+        return _image_resample("image_views", "selftok_img_views_u8", "selftok_img_views_tables_layout", "rows_dev", packed, rows, size, dtype, out, rows_dev, return_tables,
+                               empty_ok=True)
+    return _image_resample("image_views", "selftok_img_views_filter_u8", "selftok_img_views_filter_tables_layout", "rows_dev", packed, rows, size, dtype, out, rows_dev,
+                           return_tables, empty_ok=True, filter=code)
+
+
+def image_resize(packed: torch.Tensor, frames, filter, frames_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pillow's Image.resize((ow, oh), filter) of N whole RGB uint8 HWC frames inside the 1-D uint8 device tensor `packed`, IN PLACE: `frames`
+    [N, 6] on the host, per frame the source byte offset, W, H, the destination byte offset, ow, oh -- the result is written at the
+    destination, bit for bit Pillow's (csrc/image_filters.hip).  Every region must lie inside `packed` and no destination may overlap a
+    source or another destination of the call.  `filter`: 'bilinear' / 'bicubic' / 'box' or Pillow's code.  `frames_dev`: the same table
+    already on the device (int64), else it is copied here.  N = 0 does nothing.  -> `packed`."""
+    import numpy as np
+    code = image_filter_code(filter, "image_resize")
+    t = np.ascontiguousarray(np.asarray(frames), dtype=np.int64)
+    if t.ndim != 2 or t.shape[1] != 6:
+        raise _lib.SelftokHipError(f"image_resize: expected [N, 6] (source offset, W, H, destination offset, ow, oh), got {t.shape}")
+    _need_cuda(packed, frames_dev)
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise _lib.SelftokHipError(f"image_resize: `packed` must be a contiguous 1-D uint8 tensor, got {packed.dtype} {tuple(packed.shape)}")
+    N = t.shape[0]
+    if N == 0:
+        return packed
+    lib = _lib.load()
+    nbytes = lib.selftok_img_resize_u8_workspace_bytes(t.ctypes.data, N, code)
+    if nbytes == 0:
+        _lib.check(-1, "selftok_img_resize_u8_workspace_bytes")
+    if frames_dev is None:
+        frames_dev = torch.from_numpy(t).to(packed.device)
+    elif frames_dev.dtype != torch.int64 or frames_dev.numel() != 6 * N or not frames_dev.is_contiguous():
+        raise _lib.SelftokHipError("image_resize: `frames_dev` must be the contiguous int64 [N, 6] table")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
+    _lib.check(lib.selftok_img_resize_u8(_p(packed), packed.numel(), t.ctypes.data, _p(frames_dev), N, code, _p(ws), nbytes, _stream()), "selftok_img_resize_u8")
+    return packed
 
 
 def image_to_u8(img: torch.Tensor) -> torch.Tensor:

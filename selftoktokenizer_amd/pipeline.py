@@ -300,14 +300,30 @@ class SelftokPipeline():
 
     @_on_own_device
     @torch.no_grad()
-    def preprocess_u8(self, images, dtype=None, views=None) -> torch.Tensor:
+    def preprocess_u8(self, images, dtype=None, views=None, preprocess: str = "reference") -> torch.Tensor:
         """(extension) uint8 RGB HWC images -- a list of arrays of ANY sizes, or one uint8 tensor [B, H, W, 3] (host or device) -> the
         [B, 3, datasize, datasize] batch `encoding` takes, on the device: Resize(datasize) -> CenterCrop(datasize) -> NormalizeToTensor of
         the reference's user script (test.py:27-31) bit for bit (csrc/image_io.hip).  dtype: this pipeline's bf16 (default) or fp32.
         views = fn(width, height) -> a list of preprocess.View (views_five, views_ten, view_resized_crop, ...): instead [sum of views, 3,
         datasize, datasize], image by image and then view by view, each what torchvision gives on the PIL image (preprocess.apply_view_pil)
-        bit for bit (csrc/image_views.hip).  views=None is the centre crop, by the same route as before."""
+        bit for bit (csrc/image_views.hip).  views=None is the centre crop, by the same route as before.
+        preprocess: "reference" (the above); "bicubic": Resize(datasize, BICUBIC) -> CenterCrop, the views resampled with BICUBIC likewise
+        (apply_view_pil(..., filter="bicubic")); "adm": preprocess.center_crop_adm, the ADM protocol, which takes no views (csrc/image_filters.hip)."""
         dtype = dtype or self.dtype
+        if preprocess != "reference":
+            from .preprocess import _check_preprocess
+            _check_preprocess(preprocess)
+            if views is not None and preprocess == "adm":
+                raise ValueError('preprocess="adm" takes no views: the ADM protocol is one centre crop per image')
+            if torch.is_tensor(images):
+                if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+                    raise TypeError(f"expected a uint8 [B, H, W, 3] tensor, got {images.dtype} {tuple(images.shape)}")
+                images = list(images.cpu().numpy())                              # the other recipes go through the loader, whatever holds the pixels
+            loaders = self.__dict__.setdefault("_u8_loaders", {})
+            if (dtype, preprocess) not in loaders:
+                from .preprocess import DeviceLoader
+                loaders[(dtype, preprocess)] = DeviceLoader(int(self.datasize), self.device, dtype=dtype, preprocess=preprocess)
+            return loaders[(dtype, preprocess)].load(images, views=views)
         if torch.is_tensor(images):
             if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
                 raise TypeError(f"expected a uint8 [B, H, W, 3] tensor, got {images.dtype} {tuple(images.shape)}")
@@ -326,10 +342,13 @@ class SelftokPipeline():
             loaders[dtype] = DeviceLoader(int(self.datasize), self.device, dtype=dtype)
         return loaders[dtype].load(images) if views is None else loaders[dtype].load(images, views=views)
 
-    def encoding_u8(self, images, device=None, topk: int = 0, views=None):
+    def encoding_u8(self, images, device=None, topk: int = 0, views=None, preprocess: str = "reference"):
         """(extension) `encoding` from 8-bit pixels: equal to encoding(torch.stack([load_image-equivalent of each image])) -- same bf16 tensor
         into the VAE, same token ids -- without the per-image PIL resize, fp32 tensors and pageable copy on the host.  topk = k > 0: the (ids, scores)
         of `encoding_topk(..., k)` instead.  views: see preprocess_u8; one row of ids per view, equal to encoding(torch.stack([apply_view_pil(...)]))."""
+        if preprocess != "reference":                                           # see preprocess_u8: load_image(filter="bicubic") / load_image_adm are then the host twins
+            x = self.preprocess_u8(images, views=views, preprocess=preprocess)
+            return self.encoding_topk(x, k=topk, device=device) if topk else self.encoding(x, device=device)
         x = self.preprocess_u8(images) if views is None else self.preprocess_u8(images, views=views)
         return self.encoding_topk(x, k=topk, device=device) if topk else self.encoding(x, device=device)
 

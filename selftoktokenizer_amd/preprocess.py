@@ -2,7 +2,10 @@
 Resize(size) [shorter side, bilinear + antialias on PIL images] -> CenterCrop(size) -> NormalizeToTensor, and
 `save_image` for the [0,1] outputs of `decoding`; the augmented recipes (FiveCrop / TenCrop / resized_crop / hflip on a PIL image) as
 *views* -- pure integer geometry (`views_five`, `views_ten`, `view_resized_crop`), their PIL route (`apply_view_pil`) and, through
-`DeviceLoader(..., views=fn)`, the same tensors computed on the GPU (csrc/image_views.hip)."""
+`DeviceLoader(..., views=fn)`, the same tensors computed on the GPU (csrc/image_views.hip).  Besides the reference's bilinear recipe two others,
+chosen per call or per loader (`filter=`, `preprocess=`), never per view: Resize(S, BICUBIC) -> CenterCrop(S), the timm / torchvision evaluation
+default, and the ADM protocol `center_crop_adm` (BOX halvings, one BICUBIC resize, floor-divided centre crop) that published ImageNet rFID / PSNR
+tables are taken on; on the GPU through csrc/image_filters.hip."""
 from __future__ import annotations
 
 import time
@@ -16,8 +19,27 @@ from PIL import Image
 from .pipeline import NormalizeToTensor
 
 
-def resize_shorter_side(img: Image.Image, size: int) -> Image.Image:
-    """torchvision.transforms.Resize(int) on a PIL image: shorter side -> size, aspect kept, bilinear."""
+PREPROCESS = ("reference", "bicubic", "adm")                                # the recipes of DeviceLoader / preprocess_u8 / the tools
+_PIL_FILTERS = {"bilinear": Image.BILINEAR, "bicubic": Image.BICUBIC, "box": Image.BOX}
+
+
+def _pil_filter(filter):
+    """'bilinear' / 'bicubic' / 'box' or a Pillow code -> the Pillow code (the host route hands it to Image.resize as it is)"""
+    if isinstance(filter, str):
+        if filter.lower() not in _PIL_FILTERS:
+            raise ValueError(f"unknown filter {filter!r}: expected one of {sorted(_PIL_FILTERS)} or a Pillow code")
+        return _PIL_FILTERS[filter.lower()]
+    return int(filter)
+
+
+def _check_preprocess(preprocess: str) -> str:
+    if preprocess not in PREPROCESS:
+        raise ValueError(f"preprocess={preprocess!r}: expected one of {PREPROCESS}")
+    return preprocess
+
+
+def resize_shorter_side(img: Image.Image, size: int, filter="bilinear") -> Image.Image:
+    """torchvision.transforms.Resize(int, interpolation) on a PIL image: shorter side -> size, aspect kept; bilinear unless `filter` says otherwise."""
     w, h = img.size
     if (w <= h and w == size) or (h <= w and h == size):
         return img
@@ -25,7 +47,7 @@ def resize_shorter_side(img: Image.Image, size: int) -> Image.Image:
         ow, oh = size, int(size * h / w)
     else:
         oh, ow = size, int(size * w / h)
-    return img.resize((ow, oh), Image.BILINEAR)
+    return img.resize((ow, oh), _pil_filter(filter))
 
 
 def center_crop(img: Image.Image, size: int) -> Image.Image:
@@ -34,10 +56,62 @@ def center_crop(img: Image.Image, size: int) -> Image.Image:
     return img.crop((left, top, left + size, top + size))
 
 
-def load_image(path: str, size: int = 256) -> torch.Tensor:
-    """-> float tensor [3,size,size] in [-1,1] (what `SelftokPipeline.encoding` takes, stacked along dim 0)."""
+def load_image(path: str, size: int = 256, filter="bilinear") -> torch.Tensor:
+    """-> float tensor [3,size,size] in [-1,1] (what `SelftokPipeline.encoding` takes, stacked along dim 0).  filter: Resize's interpolation."""
     img = Image.open(path).convert("RGB")
-    return NormalizeToTensor()(center_crop(resize_shorter_side(img, size), size))
+    return NormalizeToTensor()(center_crop(resize_shorter_side(img, size, filter), size))
+
+
+# ---- the ADM protocol (guided-diffusion's center_crop_arr; the evaluation scripts of DiT, LlamaGen, VAR, MAR use it) ----
+MAX_ADM_HALVINGS = 8
+
+
+def center_crop_adm(img: Image.Image, S: int) -> Image.Image:
+    """the published `center_crop_arr` on PIL, the route of record: halve with BOX while the shorter side is >= 2 S, one BICUBIC resize by
+    S / shorter side (Python's round), centre crop at (side - S) // 2"""
+    while min(*img.size) >= 2 * S:
+        img = img.resize(tuple(x // 2 for x in img.size), resample=Image.BOX)
+    scale = S / min(*img.size)
+    img = img.resize(tuple(round(x * scale) for x in img.size), resample=Image.BICUBIC)
+    a = np.array(img)
+    top, left = (a.shape[0] - S) // 2, (a.shape[1] - S) // 2
+    return Image.fromarray(a[top:top + S, left:left + S])
+
+
+def load_image_adm(path: str, S: int = 256) -> torch.Tensor:
+    """`load_image` with the ADM protocol in place of Resize -> CenterCrop"""
+    return NormalizeToTensor()(center_crop_adm(Image.open(path).convert("RGB"), S))
+
+
+class AdmPlan(NamedTuple):
+    """`center_crop_adm` as numbers: frames = [(w, h), (w // 2, h // 2), ...], the source and each BOX halving; (rw, rh) what the last frame is
+    resized to with BICUBIC; (left, top) the crop's origin, by floor division (`center_crop` rounds half to even instead)"""
+    frames: tuple
+    rw: int
+    rh: int
+    left: int
+    top: int
+
+
+def adm_plan(w: int, h: int, S: int) -> AdmPlan:
+    w, h, S = int(w), int(h), int(S)
+    if w < 1 or h < 1 or S < 1:
+        raise ValueError(f"adm_plan: a {w} x {h} image and S = {S}: every one must be at least 1")
+    frames = [(w, h)]
+    while min(w, h) >= 2 * S:
+        w, h = w // 2, h // 2
+        frames.append((w, h))
+    if len(frames) - 1 > MAX_ADM_HALVINGS:
+        raise ValueError(f"adm_plan: a {frames[0][0]} x {frames[0][1]} image takes {len(frames) - 1} halvings to reach S = {S}; at most {MAX_ADM_HALVINGS} are served")
+    scale = S / min(w, h)
+    rw, rh = round(w * scale), round(h * scale)
+    return AdmPlan(tuple(frames), rw, rh, (rw - S) // 2, (rh - S) // 2)
+
+
+def view_adm(plan: AdmPlan, S: int) -> View:
+    """the last frame of an ADM chain -> its S x S output, as a view (to be resampled with BICUBIC)"""
+    w, h = plan.frames[-1]
+    return View(0, 0, w, h, plan.rw, plan.rh, plan.left, plan.top, 0, S)
 
 
 # ---- views: torchvision's five / ten-crop, resized_crop and hflip on a PIL image, as numbers (csrc/image_views.hip) ----
@@ -104,15 +178,15 @@ def mirrored(views) -> list:
     return views + [v._replace(flip=1 - v.flip) for v in views]
 
 
-def apply_view_pil(img, view, to_tensor: bool = True):
+def apply_view_pil(img, view, to_tensor: bool = True, filter="bilinear"):
     """the host route of one view with live Pillow; `img`: a PIL image or a uint8 [H, W, 3] array.  -> NormalizeToTensor's [3, size, size]
-    fp32 tensor, or with to_tensor=False the PIL image itself"""
+    fp32 tensor, or with to_tensor=False the PIL image itself.  filter: the resample's ('bilinear', 'bicubic', 'box' or a Pillow code)"""
     v = View(*view)
     S = v.size
     im = img if isinstance(img, Image.Image) else Image.fromarray(np.asarray(img))
     im = im.crop((v.x0, v.y0, v.x0 + v.bw, v.y0 + v.bh))
     if (v.rw, v.rh) != (v.bw, v.bh):
-        im = im.resize((v.rw, v.rh), Image.BILINEAR)
+        im = im.resize((v.rw, v.rh), _pil_filter(filter))
     im = im.crop((v.left, v.top, v.left + S, v.top + S))
     if v.flip:
         im = im.transpose(Image.FLIP_LEFT_RIGHT)
@@ -166,7 +240,7 @@ def _decode(item) -> np.ndarray:
 
 
 class _Staged:
-    __slots__ = ("slot", "table", "rows", "nbytes", "t_decode", "t_pack")
+    __slots__ = ("slot", "table", "rows", "chain", "nbytes", "copied", "t_decode", "t_pack")
 
 
 class DeviceLoader:
@@ -178,11 +252,17 @@ class DeviceLoader:
     `views=fn` (load and batches): fn(width, height) -> a list of `View`s of this loader's size (views_five, views_ten, view_resized_crop, ...);
     the output is then [sum of views, 3, size, size], in item order and then view order, through ops.image_views -- every source still crosses
     once.  views=None is the centre crop through ops.image_resize_crop_norm.
+    `preprocess`: "reference" (the above, untouched); "bicubic": Resize(size, BICUBIC) -> CenterCrop(size), and with views=fn the views resampled
+    with BICUBIC (ops.image_views(filter="bicubic")); "adm": `center_crop_adm` -- behind the sources the device buffer has room for each source's BOX
+    halvings (at most a third more bytes; made on the device, so the copy does not carry them), one ops.image_resize call per chain depth over the sources
+    that still need a halving, then one ops.image_views(filter="bicubic") call whose rows name each source's last frame.  views= with "adm" is
+    refused: the protocol is a single centre crop.
     `load()` stages into slot 0: do not call it while a `batches()` iteration of the SAME loader is under way (it would overwrite a
     staged batch).  Owns two thread pools: `close()` it, use it as a context manager, or let the finaliser do it."""
 
-    def __init__(self, size: int, device, dtype=torch.float32, workers: int = 8):
+    def __init__(self, size: int, device, dtype=torch.float32, workers: int = 8, preprocess: str = "reference"):
         self.size, self.device, self.dtype = int(size), torch.device(device), dtype
+        self.preprocess = _check_preprocess(preprocess)
         if self.device.type != "cuda":
             raise ValueError(f"DeviceLoader needs a GPU device, got {self.device}")
         self.workers = max(1, min(int(workers), MAX_DECODE_WORKERS))
@@ -212,20 +292,40 @@ class DeviceLoader:
             pass
 
     def _stage(self, items, slot: int, views=None) -> _Staged:
+        if views is not None and self.preprocess == "adm":
+            raise ValueError('DeviceLoader(preprocess="adm") takes no views: the ADM protocol is one centre crop per image')
         t0 = time.perf_counter()
         arrays = list(self._pool.map(_decode, items)) if self.workers > 1 and len(items) > 1 else [_decode(i) for i in items]
         t1 = time.perf_counter()
         B = len(arrays)
         table = np.empty((B, 3), dtype=np.int64)
+        plans = [adm_plan(a.shape[1], a.shape[0], self.size) for a in arrays] if self.preprocess == "adm" else None
+        last = np.empty((B, 3), dtype=np.int64)                                 # "adm": the last frame of each source's chain
+        depth = [[] for _ in range(MAX_ADM_HALVINGS)]                           # "adm": the [n, 6] frame rows of each chain depth
         at = 0
         for b, a in enumerate(arrays):
             table[b] = (at, a.shape[1], a.shape[0])
             at += (a.size + 15) // 16 * 16
-        rows = None
-        if views is not None:
+        copied = at                                                             # what crosses to the device: the tables and the sources
+        for b in range(B if plans is not None else 0):                          # room for the halved frames behind the sources, source by source
+            src = tuple(int(v) for v in table[b])
+            for d, (fw, fh) in enumerate(plans[b].frames[1:]):
+                depth[d].append(src + (at, fw, fh))
+                src = (at, fw, fh)
+                at += (fw * fh * 3 + 15) // 16 * 16
+            last[b] = src
+        rows, chain = None, []
+        if views is not None or self.preprocess != "reference":
             from . import ops
-            rows = ops.image_view_rows(table, view_rows([views(a.shape[1], a.shape[0]) for a in arrays], self.size))     # built once; _launch hands them on
-        front = table if rows is None else rows                                 # the table the kernels read travels in front of the pixels
+            if plans is not None:
+                rows = ops.image_view_rows(last, view_rows([[view_adm(p, self.size)] for p in plans], self.size))
+                chain = [np.array(d, dtype=np.int64).reshape(len(d), 6) for d in depth if d]
+            else:
+                per = views if views is not None else (lambda w, h: [view_center(w, h, self.size)])
+                rows = ops.image_view_rows(table, view_rows([per(a.shape[1], a.shape[0]) for a in arrays], self.size))   # built once; _launch hands them on
+        front = table if rows is None else rows                                 # the tables the kernels read travel in front of the pixels
+        if chain:
+            front = np.concatenate([rows.reshape(-1)] + [c.reshape(-1) for c in chain])
         head = (front.size * 8 + 63) // 64 * 64
         need = head + at
         if self._pinned[slot] is None or self._pinned[slot].numel() < need:
@@ -240,21 +340,22 @@ class DeviceLoader:
             o = head + int(table[b, 0])
             host[o:o + a.size] = a.reshape(-1)
         st = _Staged()
-        st.slot, st.table, st.rows, st.nbytes, st.t_decode, st.t_pack = slot, table, rows, need, t1 - t0, time.perf_counter() - t1
+        st.slot, st.table, st.rows, st.chain, st.nbytes, st.copied, st.t_decode, st.t_pack = slot, table, rows, chain, need, head + copied, t1 - t0, time.perf_counter() - t1
         return st
 
     def _launch(self, st: _Staged) -> torch.Tensor:
         from . import ops
         s = st.slot
         front = st.table if st.rows is None else st.rows
-        head = (front.size * 8 + 63) // 64 * 64
+        longs = front.size + sum(c.size for c in st.chain)
+        head = (longs * 8 + 63) // 64 * 64
         with torch.cuda.device(self.device):
             if self._dev[s] is None or self._dev[s].numel() < self._pinned[s].numel():
                 self._dev[s] = torch.empty(self._pinned[s].numel(), dtype=torch.uint8, device=self.device)
             if self.timing:
                 e0 = torch.cuda.Event(enable_timing=True)
                 e0.record()
-            self._dev[s][:st.nbytes].copy_(self._pinned[s][:st.nbytes], non_blocking=True)
+            self._dev[s][:st.copied].copy_(self._pinned[s][:st.copied], non_blocking=True)
             ev = torch.cuda.Event(enable_timing=self.timing)
             ev.record()
             self._copied[s] = ev
@@ -262,12 +363,17 @@ class DeviceLoader:
             if st.rows is None:
                 out = ops.image_resize_crop_norm(self._dev[s][head:st.nbytes], st.table, self.size, dtype=self.dtype, table_dev=front_dev)
             else:
-                out = ops.image_views(self._dev[s][head:st.nbytes], None, None, self.size, dtype=self.dtype, rows=st.rows, rows_dev=front_dev)
+                lo = front.size
+                for c in st.chain:                                              # depth by depth: frame d of every source that has one, from its frame d - 1
+                    ops.image_resize(self._dev[s][head:st.nbytes], c, "box", frames_dev=self._dev[s][lo * 8:(lo + c.size) * 8].view(torch.int64))
+                    lo += c.size
+                out = ops.image_views(self._dev[s][head:st.nbytes], None, None, self.size, dtype=self.dtype, rows=st.rows, rows_dev=front_dev,
+                                      filter="bilinear" if self.preprocess == "reference" else "bicubic")
             if self.timing:
                 e2 = torch.cuda.Event(enable_timing=True)
                 e2.record()
                 self.last_events = (e0, ev, e2)
-        self.last_times = {"decode_s": st.t_decode, "pack_s": st.t_pack, "bytes": int(st.nbytes)}
+        self.last_times = {"decode_s": st.t_decode, "pack_s": st.t_pack, "bytes": int(st.copied)}
         return out
 
     def load(self, items, views=None) -> torch.Tensor:

@@ -33,6 +33,7 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--seed", type=int, default=1234)
 ap.add_argument("--gemm", default=None, choices=["fp32", "f16x2", "exact", "f16"], help="exact: every operation in the reference's torch-CPU order (bit-equal pixels, the parity mode); f16: the lossy single-pass fp16 Linears (outside the 1e-3 dB of the other modes)")
 ap.add_argument("--device-io", action="store_true", help="resize / crop / normalise the decoded files on the GPU (preprocess.DeviceLoader): the same values, bit for bit")
+ap.add_argument("--preprocess", default="reference", choices=["reference", "bicubic", "adm"], help="how the files become data_size x data_size originals: the reference's Resize (bilinear) -> CenterCrop; Resize (bicubic) -> CenterCrop; or the ADM protocol center_crop_arr (BOX halvings, bicubic, floor-divided crop) that published ImageNet rFID / PSNR tables use.  By either loader route, bit for bit")
 ap.add_argument("--ssim", action="store_true", help="also the SSIM of every image (11 x 11 Gaussian window, sigma 1.5, valid region); both figures then come from one device call per batch")
 ap.add_argument("--metrics-u8", action="store_true", help="with --ssim: take PSNR and SSIM on the uint8 bytes save_image would write instead of the float tensors")
 ap.add_argument("--lpips-backbone", default=None, help="torchvision AlexNet state dict (features.{0,3,6,8,10}.{weight,bias}); with --lpips-linear: also LPIPS (alex, v0.1) of every image, on the GPU")
@@ -42,6 +43,8 @@ ap.add_argument("--fid-weights", default=None, help="pytorch-fid's pt_inception-
 ap.add_argument("--fid", action="store_true", help="with --synthetic and no weight file: rFID on the hash-generated InceptionV3 (the published definition on synthetic weights)")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file (rank 0)")
 a = ap.parse_args()
+if a.synthetic and a.preprocess != "reference":
+    ap.error("--preprocess applies to image files: --synthetic images are generated at data_size")
 
 rank, world, local = D.init_from_env()
 torch.cuda.set_device(local)
@@ -69,7 +72,7 @@ else:
     if a.limit:
         paths = paths[:a.limit]
     assert paths, f"no image files under {a.images}"
-    n, load, noise, src = len(paths), E.folder_loader(paths, a.data_size, device=dev if a.device_io else None), None, f"{len(paths)} files under {a.images}"
+    n, load, noise, src = len(paths), E.folder_loader(paths, a.data_size, device=dev if a.device_io else None, preprocess=a.preprocess), None, f"{len(paths)} files under {a.images}"
 if bool(a.lpips_backbone) != bool(a.lpips_linear):
     ap.error("--lpips-backbone and --lpips-linear go together")
 if a.lpips and not a.lpips_backbone and not a.synthetic:
@@ -94,7 +97,7 @@ if fid_net is not None:
 res = E.evaluate(pipe, load, n, batch=a.batch, decoders=decoders, noise_fn=noise, seed=a.seed, renderer_pipe=rpipe, verbose=True, **mkw)
 D.barrier()
 if rank == 0:
-    line = {"tool": "eval_psnr", "source": src, "data_size": a.data_size, "tokens": K, "gemm": pipe.model.model.gemm, "vae": pipe.vae.mode, "vae_decode": pipe.vae.decode_mode, "encoder": pipe.model.encoder.mode,
+    line = {"tool": "eval_psnr", "source": src, "data_size": a.data_size, "preprocess": a.preprocess, "tokens": K, "gemm": pipe.model.model.gemm, "vae": pipe.vae.mode, "vae_decode": pipe.vae.decode_mode, "encoder": pipe.model.encoder.mode,
             "checkpoint": a.pretrained or "synthetic (hash-generated)", "renderer_checkpoint": a.renderer_pretrained, **res,
             "readme_reference_dB": {"tokenizer_512_ckpt": 21.86, "renderer_512_ckpt": 24.14, "tokenizer_1024_ckpt": 23.06, "renderer_1024_ckpt": 26.30,
                                     "note": "README.md:89-94 (256 x 256), needs the published weights"}}

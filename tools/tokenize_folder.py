@@ -39,6 +39,7 @@ ap.add_argument("--topk", type=int, default=0, help="k in 1..8: also keep every 
 ap.add_argument("--crops", default="center", choices=["center", "five", "ten"], help="views per image: the centre crop, FiveCrop or TenCrop of the resized image")
 ap.add_argument("--resize", type=int, default=0, help="R >= data_size: shorter side of the resize before the crops (default: data_size)")
 ap.add_argument("--flip", action="store_true", help="also emit the mirror image of every view")
+ap.add_argument("--preprocess", default="reference", choices=["reference", "bicubic", "adm"], help="the reference's bilinear Resize; bicubic Resize (the views likewise); or the ADM protocol center_crop_arr, which is one centre crop per image (no --crops / --resize / --flip)")
 ap.add_argument("--out", default=None, help="prefix of the id files; nothing is written without it")
 a = ap.parse_args()
 if not 0 <= a.topk <= 8:
@@ -53,6 +54,8 @@ if a.crops != "center" or a.flip or R != a.data_size:
             "ten": lambda w, h: preprocess.views_ten(w, h, R, S)}[a.crops]
     views = (lambda w, h: preprocess.mirrored(base(w, h))) if a.flip else base
     nviews = {"center": 1, "five": 5, "ten": 10}[a.crops] * (2 if a.flip else 1)
+if views and a.preprocess == "adm":
+    ap.error("--preprocess adm is one centre crop per image: it takes no --crops, --resize or --flip")
 
 rank, world, local = D.init_from_env()
 torch.cuda.set_device(local)
@@ -77,7 +80,7 @@ else:
     lo, hi = D.shard_range(n, rank, world)
     items = paths[lo:hi]
 
-loader = preprocess.DeviceLoader(a.data_size, dev, dtype=torch.bfloat16, workers=a.workers)
+loader = preprocess.DeviceLoader(a.data_size, dev, dtype=torch.bfloat16, workers=a.workers, preprocess=a.preprocess)
 loader.timing = True
 topk_ids, topk_scores = [], []
 ids, split, marks = [], {"host_decode_s": 0.0, "pack_s": 0.0, "h2d_ms": 0.0, "resize_kernels_ms": 0.0, "encode_ms": 0.0}, []
@@ -128,7 +131,7 @@ slowest = D.max_over_ranks(wall, dev)
 D.barrier()
 if rank == 0:
     print(json.dumps({"tool": "tokenize_folder", "source": src, "images": n, "ranks": world, "batch": a.batch, "workers": loader.workers, "tokens": K,
-                      "data_size": a.data_size, "vae": pipe.vae.mode, "encoder": pipe.model.encoder.mode, "wall_s": round(slowest, 4),
+                      "data_size": a.data_size, "preprocess": a.preprocess, "vae": pipe.vae.mode, "encoder": pipe.model.encoder.mode, "wall_s": round(slowest, 4),
                       "images_per_s": round(n / slowest, 2) if slowest > 0 else None,
                       "rank0_split": {k: round(v, 4) for k, v in split.items()}, "rank0_shard": [lo, hi],
                       **extra,
