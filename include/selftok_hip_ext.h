@@ -268,6 +268,37 @@ int selftok_fid_spatial_mean_f32(const float* in, float* out, int N, int npix, i
 size_t selftok_fid_stats_workspace_bytes(int N, int D);
 int selftok_fid_stats(const float* x, double* mu, double* sigma, void* workspace, size_t workspace_bytes, int N, int D, hipStream_t stream);
 
+/* ---- generative-model metrics: k-NN radii and manifold membership on squared distances, Inception Score reductions ------------
+ * The kernels of selftoktokenizer_amd/genmetrics.py (GEN_METRICS_DEFINITION states the metrics; csrc/gen_metrics_shared.h states the
+ * arithmetic of d2(u, v) = |u|^2 + |v|^2 - 2 u.v clamped at +0, SQUARED and never square-rooted, its bits a function of the two rows
+ * alone; csrc/gen_metrics.hip states the selection and every summation order).  Rows are contiguous fp32 [., D], D a multiple of 16 in
+ * 16 .. 2048, 16-byte aligned.  The N x N / M x N distance matrix is never stored.  Every refusal is decided on the host before any
+ * launch and returns SELFTOK_EINVAL with a message (the queries return 0 with the message set); nothing allocates, synchronises or
+ * keeps state; no atomics.
+ *
+ * selftok_knn_radius_f32: a [N, D] -> r2[j] = the k-th smallest d2(a_j, a_i) over i != j (the row's own INDEX is skipped, not its value:
+ *   a bit-copy of row j is a neighbour, at a distance within E of 0 -- the same bits through both entries).  1 <= k <= 8, N > k.  A NaN distance is never a neighbour; a row with fewer
+ *   than k non-NaN neighbours (a row that holds a NaN) gets r2 = NaN and changes no other row's radius.
+ * selftok_manifold_member_f32: x [M, D], a [N, D], r2 [N] -> member[i] = 1 if d2(x_i, a_j) <= r2[j] for some j, else 0 (int32).  The
+ *   comparison is <=, false against NaN.  M == 0 returns 0 without a launch.
+ * `split`: launch-shape override, the number of column splits (0 = automatic; values above min(64, ceil(N / 128)) are clamped); the
+ *   outputs never depend on it.  Workspace (row norms, and per column part and row the k smallest distances / one flag) from the
+ *   queries; nothing beyond the stated size is touched.
+ * selftok_is_colmean: logits [N, C] fp32 -> colmean [ceil(N / split_size), C] fp64: per consecutive split of split_size rows (the last,
+ *   partial split included) the column means of p = softmax(logits) taken in fp64, chunks of 256 rows and a fixed pairwise tree.
+ * selftok_is_kl_rows: kl[n] = sum_y p_ny (log p_ny - log colmean[n / split_size][y]) in fp64; a term with p_ny == 0 is 0.
+ *   N, C, split_size >= 1, N * C < 2^31, at most 65535 chunks over all splits. */
+size_t selftok_knn_radius_f32_workspace_bytes(int N, int D, int k);
+int selftok_knn_radius_f32(const float* a, float* r2, void* workspace, size_t workspace_bytes, int N, int D, int k, int split, hipStream_t stream);
+size_t selftok_manifold_member_f32_workspace_bytes(int M, int N, int D);
+int selftok_manifold_member_f32(const float* x, const float* a, const float* r2, int* member, void* workspace, size_t workspace_bytes, int M, int N, int D,
+                                int split, hipStream_t stream);
+size_t selftok_is_colmean_workspace_bytes(int N, int C, int split_size);
+int selftok_is_colmean(const float* logits, double* colmean, void* workspace, size_t workspace_bytes, int N, int C, int split_size, hipStream_t stream);
+size_t selftok_is_kl_rows_workspace_bytes(int N, int C, int split_size);
+int selftok_is_kl_rows(const float* logits, const double* colmean, double* kl, void* workspace, size_t workspace_bytes, int N, int C, int split_size,
+                       hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

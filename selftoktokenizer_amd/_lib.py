@@ -118,6 +118,14 @@ EXT_SIGNATURES = {
     "selftok_fid_spatial_mean_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "selftok_fid_stats_workspace_bytes": (_sz, [_i, _i]),
     "selftok_fid_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "selftok_knn_radius_f32_workspace_bytes": (_sz, [_i, _i, _i]),
+    "selftok_knn_radius_f32": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "selftok_manifold_member_f32_workspace_bytes": (_sz, [_i, _i, _i]),
+    "selftok_manifold_member_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "selftok_is_colmean_workspace_bytes": (_sz, [_i, _i, _i]),
+    "selftok_is_colmean": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "selftok_is_kl_rows_workspace_bytes": (_sz, [_i, _i, _i]),
+    "selftok_is_kl_rows": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
 }
 
 

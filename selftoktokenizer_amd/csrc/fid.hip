@@ -25,6 +25,7 @@
 #include "common.h"
 #include "conv_f32_shared.h"
 #include "u8_shared.h"
+#include "chunk_tree.h"
 #include "selftok_hip_ext.h"
 #include <stdio.h>
 
@@ -127,36 +128,8 @@ __global__ void __launch_bounds__(NT) fid_mean_kernel(const float* __restrict__ 
 }
 
 // ---- statistics ----
-constexpr int SCH = 256;                                          // rows per chunk
-constexpr int LEVELS = 23;                                        // 2^23 chunks of 256 rows: every N below 2^31
+constexpr int SCH = 256;                                          // rows per chunk (csrc/chunk_tree.h: the tree across chunks)
 constexpr int ST = 16, SSUB = 32;                                 // covariance tile side; rows staged per step
-
-// the pairwise tree of a binary counter over the chunk values, in registers (every index is a compile-time constant)
-struct chunk_tree {
-    double lvl[LEVELS];
-    unsigned n;
-    __device__ __forceinline__ void init() { n = 0; }
-    __device__ __forceinline__ void push(double v)
-    {
-        bool placed = false;
-#pragma unroll
-        for (int l = 0; l < LEVELS; ++l) {
-            if (placed) continue;
-            if ((n >> l) & 1u) v = lvl[l] + v;                    // (earlier 2^l chunks) + (later 2^l chunks)
-            else { lvl[l] = v; placed = true; }
-        }
-        ++n;
-    }
-    __device__ __forceinline__ double total() const
-    {
-        double t = 0.0;
-        bool have = false;
-#pragma unroll
-        for (int l = 0; l < LEVELS; ++l)
-            if ((n >> l) & 1u) { t = have ? lvl[l] + t : lvl[l]; have = true; }
-        return t;
-    }
-};
 
 // grid (ceil(D / 64), chunks): ws[chunk * D + d] = the chunk's sum of column d
 __global__ void __launch_bounds__(64) fid_colsum_kernel(const float* __restrict__ x, double* __restrict__ ws, int N, int D)

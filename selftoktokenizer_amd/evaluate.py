@@ -78,16 +78,26 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     "rfid" with `fid=` a fid.InceptionNet (no default network either): the device route; the pool3 features of the originals (once) and of every decoder's
     reconstructions are collected per batch and gathered like the per-image values, and the statistics are taken of the GATHERED matrices, so the figure does
     not depend on the sharding.  Every decoder's dict gains `rfid`, `rfid_n` and `rfid_rank_deficient` (fewer than 2049 images: the covariances are singular
-    and the figure is only comparable at the same N); `metric_definition["rfid"]` states the definition and the weights' source; metrics_u8 applies."""
+    and the figure is only comparable at the same N); `metric_definition["rfid"]` states the definition and the weights' source; metrics_u8 applies.
+    "precision_recall" with `fid=` likewise: improved precision / recall (genmetrics.GEN_METRICS_DEFINITION, k = 3) on the same gathered pool3 features, the
+    originals as the reference set against every decoder's reconstructions; every decoder's dict gains `precision`, `recall` and their integer counts, and
+    `metric_definition["precision_recall"]` states the definition.  Needs more than 3 images."""
     with_lpips = "lpips" in metrics and lpips is not None
     with_fid = "rfid" in metrics and fid is not None
-    bad = [m for m in metrics if m not in ("psnr", "ssim") and not (m == "lpips" and with_lpips) and not (m == "rfid" and with_fid)]
+    with_pr = "precision_recall" in metrics and fid is not None
+    bad = [m for m in metrics if m not in ("psnr", "ssim") and not (m == "lpips" and with_lpips) and not (m == "rfid" and with_fid) and not (m == "precision_recall" and with_pr)]
     if bad or not metrics:
         raise ValueError(f"metrics {tuple(metrics)!r}: expected a non-empty subset of ('psnr', 'ssim')" + (", or 'lpips' together with lpips=<LpipsNet>" if "lpips" in bad else "")
-                         + (", or 'rfid' together with fid=<InceptionNet>" if "rfid" in bad else ""))
+                         + (", or 'rfid' together with fid=<InceptionNet>" if "rfid" in bad else "")
+                         + (", or 'precision_recall' together with fid=<InceptionNet>" if "precision_recall" in bad else ""))
     if with_fid and n_images < 2:
         raise ValueError(f"'rfid' needs at least 2 images (a covariance), got {n_images}")
-    on_device = "ssim" in metrics or with_lpips or with_fid
+    if with_pr:
+        from . import genmetrics as GM
+        if n_images <= GM.K_DEFAULT:
+            raise ValueError(f"'precision_recall' needs more than k = {GM.K_DEFAULT} images (a k-th neighbour), got {n_images}")
+    with_feats = with_fid or with_pr
+    on_device = "ssim" in metrics or with_lpips or with_feats
     if metrics_u8 and not on_device:
         raise ValueError("metrics_u8 needs 'ssim' in `metrics` (the device route); the host PSNR route is the float one")
     world, rank = D.world_size(), D.rank()       # the dist module's view: sharding and the gather below must agree (ADVICE r5)
@@ -105,7 +115,7 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
         tokens = pipe.encoding(imgs, device=pipe.device)
         ids = tokens.detach().cpu().numpy()                       # the reference round-trips the ids through a host .npy (test.py:38-39)
         ids_all.append(ids)
-        if with_fid:
+        if with_feats:
             feats[None].append(fid.pool3(imgs, signed=True, quantize=metrics_u8))
         for d in decoders:
             if d == "diffusion":
@@ -121,7 +131,7 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
                 if with_lpips:
                     m = torch.cat([m, lpips(rec.detach(), imgs, original_signed=True, quantize=metrics_u8)[:, None]], dim=1)      # [b, 3]
                 vals[d].append(m)
-                if with_fid:
+                if with_feats:
                     feats[d].append(fid.pool3(rec.detach(), signed=False, quantize=metrics_u8))
             else:
                 vals[d].append(psnr_each(rec, imgs))
@@ -129,9 +139,15 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
             so_far = (lambda d: float(psnr_of_mse(torch.cat(vals[d])[:, 1].cpu().numpy()).mean())) if on_device else (lambda d: np.concatenate(vals[d]).mean())
             print(f"[eval] images {b0}..{b1 - 1} of shard {lo}..{hi - 1}: " + ", ".join(f"{d} {so_far(d):.4f} dB so far" for d in decoders), flush=True)
     out = {"images": int(n_images), "ranks": world, "batch": int(batch), "shard": [int(lo), int(hi)]}
-    if with_fid:
+    if with_feats:
         from . import fid as FD
-        gathered = lambda key: D.all_gather_rows(torch.cat(feats[key]) if feats[key] else torch.zeros(0, FD.FEATURES, dtype=torch.float32, device=pipe.device), counts)
+        held = {}                                                 # every feature matrix is gathered ONCE, whichever figures read it
+
+        def gathered(key):
+            if key not in held:
+                held[key] = D.all_gather_rows(torch.cat(feats[key]) if feats[key] else torch.zeros(0, FD.FEATURES, dtype=torch.float32, device=pipe.device), counts)
+            return held[key]
+    if with_fid:
         mu0, sigma0 = (t.cpu().numpy() for t in FD.statistics(gathered(None)))
     for d in decoders:
         if on_device:
@@ -144,6 +160,8 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
                 out[d].update({"lpips_mean": float(allv[:, 2].mean()) if ssim.size else float("nan"), "lpips_each": [round(float(v), 9) for v in allv[:, 2]]})
             if with_fid:
                 out[d].update({"rfid": FD.frechet_distance(*FD.statistics(gathered(d)), mu0, sigma0), "rfid_n": int(n_images), "rfid_rank_deficient": n_images <= FD.FEATURES})
+            if with_pr:
+                out[d].update({k: v for k, v in GM.precision_recall(gathered(None), gathered(d)).items() if k not in ("n_ref", "n_gen", "k")})
             continue
         mine = torch.from_numpy(np.concatenate(vals[d]) if vals[d] else np.zeros(0)).to(torch.float64)
         allv = D.all_gather_rows(mine.to(pipe.device), counts).cpu().numpy()      # returns `mine` when there is no exchange to perform
@@ -155,6 +173,8 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
             out["metric_definition"]["lpips"] = dict(LPIPS_DEFINITION, weights=lpips.source)
         if with_fid:
             out["metric_definition"]["rfid"] = dict(FD.FID_DEFINITION, weights=fid.source, resized=bool(fid.resize))
+        if with_pr:
+            out["metric_definition"]["precision_recall"] = dict(GM.GEN_METRICS_DEFINITION, weights=fid.source, resized=bool(fid.resize), n=int(n_images))
     out["token_ids_first_image"] = ids_all[0][0, :8].tolist() if ids_all else []
     return out
 
@@ -177,3 +197,86 @@ def folder_loader(paths: Sequence[str], size: int, device=None, preprocess: str 
             return torch.stack([P.load_image(p, size, filter="bicubic") for p in paths[lo:hi]])
         return torch.stack([P.load_image(p, size) for p in paths[lo:hi]])
     return load
+
+
+COMPARE_METRICS = ("fid", "is", "precision", "recall")
+
+
+def compare_sets(load_ref: Callable[[int, int], torch.Tensor], n_ref: int, load_gen: Callable[[int, int], torch.Tensor], n_gen: int, fid=None,
+                 metrics: Sequence[str] = COMPARE_METRICS, batch: int = 64, k: Optional[int] = None, split_size: Optional[int] = None, device=None) -> Dict:
+    """Two image sets against each other, the figures of the ADM / LlamaGen protocol that this project defines: FID, Inception Score (of the generated set),
+    improved precision and recall.  load_ref(lo, hi) / load_gen(lo, hi) -> float tensor [hi - lo, 3, H, W] in [-1, 1] (host or device; load_gen may decode
+    token ids through a pipeline); each rank walks its contiguous shard (dist.shard_range) of either set in batches of `batch`, the pool3 features (and, for
+    "is", the fc logits) are gathered to every rank and every figure is taken of the GATHERED matrices, so it does not depend on the sharding or the batch.
+    `fid`: a fid.InceptionNet (no default network: the weights are not shipped), built with logits=True when "is" is asked for.  k: neighbours of
+    precision / recall (default 3); split_size: rows per Inception Score split (default 5000)."""
+    from . import fid as FD, genmetrics as GM
+    metrics = tuple(metrics)
+    bad = [m for m in metrics if m not in COMPARE_METRICS]
+    if bad or not metrics:
+        raise ValueError(f"metrics {metrics!r}: expected a non-empty subset of {COMPARE_METRICS}")
+    if fid is None:
+        raise ValueError("compare_sets needs fid=<InceptionNet> (the weights are not shipped, so there is no default network)")
+    k = GM.K_DEFAULT if k is None else int(k)
+    split_size = GM.SPLIT_SIZE if split_size is None else int(split_size)
+    with_is, with_pr = "is" in metrics, "precision" in metrics or "recall" in metrics
+    if with_is and fid.fc_packed is None:
+        raise ValueError("compare_sets: 'is' needs a network built with logits=True")
+    if "fid" in metrics and min(n_ref, n_gen) < 2:
+        raise ValueError(f"'fid' needs at least 2 images per set (a covariance), got {n_ref} and {n_gen}")
+    if with_pr and (min(n_ref, n_gen) <= k or not 1 <= k <= GM.K_MAX):
+        raise ValueError(f"'precision' / 'recall' need 1 <= k <= {GM.K_MAX} and more than k images per set, got k {k}, {n_ref} and {n_gen} images")
+    if n_gen < 1 or n_ref < 1 or split_size < 1 or batch < 1:
+        raise ValueError(f"compare_sets: need n_ref, n_gen, batch, split_size >= 1, got {n_ref}, {n_gen}, {batch}, {split_size}")
+    device = fid.device if device is None else torch.device(device)
+    world, rank = D.world_size(), D.rank()
+
+    def walk(load, n, want_logits):
+        lo, hi = D.shard_range(n, rank, world)
+        counts = [D.shard_range(n, r, world)[1] - D.shard_range(n, r, world)[0] for r in range(world)]
+        f, lg = [], []
+        for b0 in range(lo, hi, batch):
+            b1 = min(b0 + batch, hi)
+            f.append(fid.pool3(load(b0, b1).to(device), signed=True))
+            if want_logits:
+                lg.append(fid.logits(f[-1]))
+        cat = lambda ts, width: D.all_gather_rows(torch.cat(ts) if ts else torch.zeros(0, width, dtype=torch.float32, device=device), counts)
+        return cat(f, FD.FEATURES), (cat(lg, FD.CLASSES) if want_logits else None)
+
+    fr, _ = walk(load_ref, n_ref, False)
+    fg, lg = walk(load_gen, n_gen, with_is)
+    out = {"n_ref": int(n_ref), "n_gen": int(n_gen), "ranks": world, "batch": int(batch)}
+    definition = {"weights": fid.source, "resized": bool(fid.resize)}
+    if "fid" in metrics:
+        out["fid"] = FD.frechet_distance(*FD.statistics(fg), *FD.statistics(fr))
+        out["fid_rank_deficient"] = min(n_ref, n_gen) <= FD.FEATURES
+        definition["fid"] = FD.FID_DEFINITION
+    if with_is:
+        out["is"] = GM.inception_score(lg, split_size)
+        out["split_size"] = split_size
+    if with_pr:
+        pr = GM.precision_recall(fr, fg, k)
+        out.update({key: v for key, v in pr.items() if key.split("_")[0] in metrics or key == "k"})
+    if with_is or with_pr:
+        definition["gen_metrics"] = GM.GEN_METRICS_DEFINITION
+    out["metric_definition"] = definition
+    return out
+
+
+def index_noise(seed: int, latent: int = 32) -> Callable[[int, int], torch.Tensor]:
+    """noise_fn(lo, hi) -> [hi - lo, 16, latent, latent]: the decode-start noise of item i comes from a CPU generator seeded `seed + i`, so what item i decodes
+    to depends on neither the batch nor the sharding (the global generator `evaluate` seeds with seed + rank does)"""
+    return lambda lo, hi: torch.stack([torch.randn(16, latent, latent, generator=torch.Generator().manual_seed(int(seed) + i)) for i in range(lo, hi)]) \
+        if hi > lo else torch.zeros(0, 16, latent, latent)
+
+
+def npz_loader(path: str, key: str = "arr_0") -> "tuple[Callable[[int, int], torch.Tensor], int]":
+    """(load_batch, n) over an ADM-style sample file: an .npz whose `arr_0` is uint8 [N, H, W, 3] -> float32 [b, 3, H, W] in [-1, 1], byte / 127.5 - 1 (the
+    NormalizeToTensor expression of the folder route)"""
+    with np.load(path) as z:
+        if key not in z:
+            raise KeyError(f"{path}: key {key!r} is missing")
+        arr = np.asarray(z[key])
+    if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[3] != 3:
+        raise ValueError(f"{path}: expected uint8 [N, H, W, 3], got {arr.dtype} {arr.shape}")
+    return (lambda lo, hi: torch.from_numpy(arr[lo:hi]).permute(0, 3, 1, 2).float() / 127.5 - 1.0), int(arr.shape[0])

@@ -22,6 +22,7 @@ BN_EPS = 1e-3
 SIDE = 299                    # the network's own input side: what `resize=True` brings an image to
 MIN_SIDE = 75                 # smallest H, W that leaves one pixel at the last map
 FEATURES = 2048
+CLASSES = 1008                # the fc head of the 2015 network: what the Inception Score reads (genmetrics.py)
 CHUNK_BYTES = 1 << 30         # activations of one internal chunk of images stay below this (one image at 299 x 299 is 45 MB: 22 images)
 
 
@@ -114,6 +115,11 @@ def state_shapes() -> Dict[str, Tuple[int, ...]]:
     return out
 
 
+def fc_shapes() -> Dict[str, Tuple[int, ...]]:
+    """the fc head's two tensors (state_shapes() lists the 94 units only): read when a network is built with logits=True"""
+    return {"fc.weight": (CLASSES, FEATURES), "fc.bias": (CLASSES,)}
+
+
 class _Runner:
     """walks the network once: `dry` only sizes the activations (meta tensors), otherwise they come from `alloc` and the kernels run"""
 
@@ -201,12 +207,12 @@ def map_sizes(H: int, W: int) -> List[Tuple[int, int]]:
 class InceptionNet:
     """net.pool3(images, signed) -> fp32 [B, 2048] on the device.  Built from a state dict in the pt_inception-2015-12-05 key layout."""
 
-    def __init__(self, state: Dict[str, torch.Tensor], device, source):
+    def __init__(self, state: Dict[str, torch.Tensor], device, source, logits: bool = False):
         self.device = torch.device(device)
         self.source = source
         self.chunk_images: Optional[int] = None                   # None: sized from CHUNK_BYTES; the tests set it to walk the chunk edges
         self.resize = True                                        # what pool3(resize=None) does, evaluate()'s route: False feeds the images straight in
-        shapes = state_shapes()
+        shapes = dict(state_shapes(), **(fc_shapes() if logits else {}))
         for key, shape in shapes.items():
             if key not in state:
                 raise KeyError(f"FID InceptionV3: key {key!r} is missing")
@@ -217,6 +223,10 @@ class InceptionNet:
             w, b = fold_bn(state[f"{name}.conv.weight"].detach().cpu(), {leaf: state[f"{name}.bn.{leaf}"].detach().cpu() for leaf in BN_LEAVES})
             self.packed[name] = ops.lpips_pack_conv_weight(w).to(self.device)
             self.bias[name] = b.contiguous().to(self.device)
+        self.fc_packed = self.fc_bias = None                      # logits=True: the fc head as a 1 x 1 convolution on the 1 x 1 pool3 map
+        if logits:
+            self.fc_packed = ops.lpips_pack_conv_weight(state["fc.weight"].detach().cpu().float().view(CLASSES, FEATURES, 1, 1)).to(self.device)
+            self.fc_bias = state["fc.bias"].detach().cpu().float().contiguous().to(self.device)
 
     # ---- construction ----
     @staticmethod
@@ -237,15 +247,24 @@ class InceptionNet:
                 sd[key] = synth.hash_uniform(seed, shape, -0.1, 0.1)
         return sd
 
-    @classmethod
-    def synthetic(cls, device) -> "InceptionNet":
-        return cls(cls.synthetic_tensors(), device, "synthetic")
+    @staticmethod
+    def synthetic_fc_tensors() -> Dict[str, torch.Tensor]:
+        """the fc head, hash-generated like the units: weight uniform in +-4 * sqrt(3 / 2048) (the gain keeps the class probabilities of different images
+        apart), bias in [-0.1, 0.1]"""
+        a = 4.0 * math.sqrt(3.0 / FEATURES)
+        return {"fc.weight": synth.hash_uniform(synth.name_seed("fid.inception.fc.weight"), (CLASSES, FEATURES), -a, a),
+                "fc.bias": synth.hash_uniform(synth.name_seed("fid.inception.fc.bias"), (CLASSES,), -0.1, 0.1)}
 
     @classmethod
-    def from_files(cls, pth: str, device) -> "InceptionNet":
+    def synthetic(cls, device, logits: bool = False) -> "InceptionNet":
+        return cls(dict(cls.synthetic_tensors(), **(cls.synthetic_fc_tensors() if logits else {})), device, "synthetic", logits)
+
+    @classmethod
+    def from_files(cls, pth: str, device, logits: bool = False) -> "InceptionNet":
         """pytorch-fid's pt_inception-2015-12-05 state dict: keys <layer>.conv.weight and <layer>.bn.{weight,bias,running_mean,running_var} of the 94 units.
-        A missing key or a wrong shape is an error; fc.*, AuxLogits.*, num_batches_tracked and any other key are ignored."""
-        return cls(torch.load(pth, map_location="cpu", weights_only=True), device, os.path.basename(pth))
+        A missing key or a wrong shape is an error; fc.*, AuxLogits.*, num_batches_tracked and any other key are ignored.  logits=True also reads
+        fc.weight [1008, 2048] and fc.bias [1008] (missing or misshapen: an error), for net.logits / net.features."""
+        return cls(torch.load(pth, map_location="cpu", weights_only=True), device, os.path.basename(pth), logits)
 
     # ---- the network ----
     def _check(self, images, resize):
@@ -305,6 +324,24 @@ class InceptionNet:
         resize=False feeds H x W >= 75 x 75 straight in; None: self.resize (True unless set otherwise).  No synchronisation.  Large batches are walked in chunks
         of images; a value does not depend on the chunking."""
         return self._run(images, signed, quantize, self.resize if resize is None else resize, False)[0]
+
+    def logits(self, pool3: torch.Tensor) -> torch.Tensor:
+        """pool3 [B, 2048] fp32 on the device -> the fc logits, fp32 [B, 1008]: pool3 . W^T + b as a 1 x 1 convolution on a 1 x 1 map (ops.fid_conv2d, no ReLU),
+        so a row's logits are a function of that row alone in the convolution's stated arithmetic.  Needs a network built with logits=True."""
+        if self.fc_packed is None:
+            raise _lib.SelftokHipError("fid: this network was built without the fc head: build it with logits=True (InceptionNet.synthetic / from_files)")
+        if pool3.dim() != 2 or pool3.shape[1] != FEATURES or pool3.dtype != torch.float32:
+            raise _lib.SelftokHipError(f"fid: logits expects float32 pool3 features [B, {FEATURES}], got {pool3.dtype} {tuple(pool3.shape)}")
+        ops._need_cuda(pool3)
+        B = pool3.shape[0]
+        if B == 0:
+            return torch.empty(0, CLASSES, dtype=torch.float32, device=pool3.device)
+        return ops.fid_conv2d(pool3.contiguous().view(B, 1, 1, FEATURES), self.fc_packed, self.fc_bias, CLASSES, 1, 1, 1, 0, 0, relu=False).view(B, CLASSES)
+
+    def features(self, images: torch.Tensor, signed: bool, quantize: bool = False, resize: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(pool3 [B, 2048], logits [B, 1008]) of one walk of the network: pool3() followed by logits()"""
+        f = self.pool3(images, signed, quantize, resize)
+        return f, self.logits(f)
 
     def stages(self, images: torch.Tensor, signed: bool, quantize: bool = False, resize: Optional[bool] = None) -> Dict[str, torch.Tensor]:
         """the network input, the stem's and every block's output as [B, C, h, w] fp32 and "pool3" [B, 2048]: what the tests compare stage by stage"""

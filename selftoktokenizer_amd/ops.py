@@ -1532,3 +1532,85 @@ def fid_stats(x: torch.Tensor, mu: Optional[torch.Tensor] = None, sigma: Optiona
     ws = lpips_workspace(x.device, nbytes) if workspace is None else workspace
     _lib.check(lib.selftok_fid_stats(_p(x), _p(mu), _p(sigma), _p(ws), ws.numel() * ws.element_size(), N, D, _stream()), "selftok_fid_stats")
     return mu, sigma
+
+
+# ---- generative-model metrics (csrc/gen_metrics.hip, include/selftok_hip_ext.h): squared-distance k-NN radii, manifold membership, Inception Score ----
+def _gm_rows(name: str, t: torch.Tensor) -> torch.Tensor:
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise _lib.SelftokHipError(f"{name}: expected a float32 [rows, D] tensor, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _gm_workspace(what: str, nbytes: int, device, workspace: Optional[torch.Tensor]) -> torch.Tensor:
+    if nbytes == 0:
+        _lib.check(-1, what)
+    return lpips_workspace(device, nbytes) if workspace is None else workspace
+
+
+def knn_radius(a: torch.Tensor, k: int = 3, *, split: int = 0, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a [N, D] fp32 -> r2 [N] fp32: the k-th smallest SQUARED distance of every row to the other rows (its own index skipped), 1 <= k <= 8, N > k.
+    The N x N matrix is never stored.  split: launch-shape override (0 = automatic), never visible in the result."""
+    a = _gm_rows("knn_radius", a)
+    _need_cuda(a, out, workspace)
+    N, D = a.shape
+    lib = _lib.load()
+    ws = _gm_workspace("selftok_knn_radius_f32_workspace_bytes", lib.selftok_knn_radius_f32_workspace_bytes(N, D, int(k)), a.device, workspace)
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=a.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (N,) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"knn_radius: `out` must be a contiguous float32 [{N}], got {out.dtype} {tuple(out.shape)}")
+    _lib.check(lib.selftok_knn_radius_f32(_p(a), _p(out), _p(ws), ws.numel() * ws.element_size(), N, D, int(k), int(split), _stream()), "selftok_knn_radius_f32")
+    return out
+
+
+def manifold_member(x: torch.Tensor, a: torch.Tensor, r2: torch.Tensor, *, split: int = 0, out: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [M, D], a [N, D], r2 [N] fp32 -> int32 [M]: 1 where d2(x_i, a_j) <= r2[j] for some j.  M == 0 gives an empty tensor without a launch."""
+    x, a = _gm_rows("manifold_member", x), _gm_rows("manifold_member", a)
+    _need_cuda(x, a, r2, out, workspace)
+    M, D = x.shape
+    N = a.shape[0]
+    if a.shape[1] != D or r2.dtype != torch.float32 or tuple(r2.shape) != (N,):
+        raise _lib.SelftokHipError(f"manifold_member: expected x [M, D], a [N, D] and a float32 r2 [N], got {tuple(x.shape)}, {tuple(a.shape)}, {r2.dtype} {tuple(r2.shape)}")
+    r2 = r2.contiguous()
+    lib = _lib.load()
+    ws = _gm_workspace("selftok_manifold_member_f32_workspace_bytes", lib.selftok_manifold_member_f32_workspace_bytes(M, N, D), x.device, workspace)
+    if out is None:
+        out = torch.empty(M, dtype=torch.int32, device=x.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (M,) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"manifold_member: `out` must be a contiguous int32 [{M}], got {out.dtype} {tuple(out.shape)}")
+    _lib.check(lib.selftok_manifold_member_f32(_p(x) if M else None, _p(a), _p(r2), _p(out) if M else None, _p(ws), ws.numel() * ws.element_size(), M, N, D, int(split),
+                                               _stream()), "selftok_manifold_member_f32")
+    return out
+
+
+def _is_logits(name: str, logits: torch.Tensor) -> torch.Tensor:
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise _lib.SelftokHipError(f"{name}: expected float32 logits [N, C], got {logits.dtype} {tuple(logits.shape)}")
+    return logits.contiguous()
+
+
+def is_colmean(logits: torch.Tensor, split_size: int, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """logits [N, C] fp32 -> fp64 [ceil(N / split_size), C]: the column means of softmax(logits) over every consecutive split (the last, partial one included)"""
+    _need_cuda(logits, workspace)
+    logits = _is_logits("is_colmean", logits)
+    N, C = logits.shape
+    lib = _lib.load()
+    ws = _gm_workspace("selftok_is_colmean_workspace_bytes", lib.selftok_is_colmean_workspace_bytes(N, C, int(split_size)), logits.device, workspace)
+    out = torch.empty(-(-N // int(split_size)), C, dtype=torch.float64, device=logits.device)
+    _lib.check(lib.selftok_is_colmean(_p(logits), _p(out), _p(ws), ws.numel() * ws.element_size(), N, C, int(split_size), _stream()), "selftok_is_colmean")
+    return out
+
+
+def is_kl_rows(logits: torch.Tensor, colmean: torch.Tensor, split_size: int, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """kl[n] = sum_y p_ny (log p_ny - log colmean[n // split_size, y]) in fp64, p = softmax(logits[n]) -> fp64 [N]"""
+    _need_cuda(logits, colmean, workspace)
+    logits = _is_logits("is_kl_rows", logits)
+    N, C = logits.shape
+    lib = _lib.load()
+    ws = _gm_workspace("selftok_is_kl_rows_workspace_bytes", lib.selftok_is_kl_rows_workspace_bytes(N, C, int(split_size)), logits.device, workspace)
+    if colmean.dtype != torch.float64 or tuple(colmean.shape) != (-(-N // int(split_size)), C) or not colmean.is_contiguous():
+        raise _lib.SelftokHipError(f"is_kl_rows: `colmean` must be a contiguous float64 {(-(-N // int(split_size)), C)}, got {colmean.dtype} {tuple(colmean.shape)}")
+    out = torch.empty(N, dtype=torch.float64, device=logits.device)
+    _lib.check(lib.selftok_is_kl_rows(_p(logits), _p(colmean), _p(out), _p(ws), ws.numel() * ws.element_size(), N, C, int(split_size), _stream()), "selftok_is_kl_rows")
+    return out
