@@ -299,6 +299,26 @@ size_t selftok_is_kl_rows_workspace_bytes(int N, int C, int split_size);
 int selftok_is_kl_rows(const float* logits, const double* colmean, double* kl, void* workspace, size_t workspace_bytes, int N, int C, int split_size,
                        hipStream_t stream);
 
+/* ---- density / coverage, nearest neighbours and KID on the same features (csrc/gen_metrics_kdc.hip) --------------------------------
+ * The pair arithmetic is csrc/gen_metrics_shared.h's: d2 and the dot products carry the bits the two entries above produce.  Limits,
+ * alignment, refusals and the `split` override are theirs too.  Unpinned against torch-fidelity and prdc.
+ *
+ * manifold_count_nn: x [M, D], a [N, D], r2 [N] or null -> count[i] = #{ j : d2(x_i, a_j) <= r2[j] } (int32; <= as the membership entry,
+ *   false against NaN; count is null exactly when r2 is, and then no count is taken), nn_d2[i] = the smallest non-NaN d2(x_i, a_j),
+ *   nn_idx[i] = the lowest j whose d2 has those bits (the minimum of (bits of d2 << 32) | j as an unsigned 64-bit integer); a query with
+ *   no non-NaN distance gets nn_d2 = NaN, nn_idx = -1.  Rows past the end of the set are masked by index.  M == 0 returns 0 without a
+ *   launch.  Workspace: the row norms, and per column part and query one 64-bit key and one count.
+ * kid_sums: xs, ys [S * m, D]: subset s is rows s * m .. s * m + m - 1 of either -> sums [S, 3] fp64 = { XX, YY, XY } with
+ *   k(u, v) = (u.v / D + 1)^3: the dot product c is the shared fp32 chain, t = (double)c / (double)D + 1.0 and (t * t) * t are fp64;
+ *   XX = sum over positions i != j of k(x_i, x_j) (the diagonal excluded by position, not by value), YY likewise, XY = sum over all i, j.
+ *   The summation order is fixed (csrc/gen_metrics_kdc.hip states it); a subset's triple depends on its own 2 m rows alone.
+ *   1 <= S <= 65535, 2 <= m <= 2^22, S * m * D < 2^31.  Workspace: one fp64 per (subset, sum, 128 x 128 tile). */
+size_t selftok_manifold_count_nn_f32_workspace_bytes(int M, int N, int D);
+int selftok_manifold_count_nn_f32(const float* x, const float* a, const float* r2, int* count, float* nn_d2, int* nn_idx, void* workspace, size_t workspace_bytes,
+                                  int M, int N, int D, int split, hipStream_t stream);
+size_t selftok_kid_sums_f32_workspace_bytes(int S, int m, int D);
+int selftok_kid_sums_f32(const float* xs, const float* ys, double* sums, void* workspace, size_t workspace_bytes, int S, int m, int D, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,10 @@ EXT_SIGNATURES = {
     "selftok_is_colmean": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "selftok_is_kl_rows_workspace_bytes": (_sz, [_i, _i, _i]),
     "selftok_is_kl_rows": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "selftok_manifold_count_nn_f32_workspace_bytes": (_sz, [_i, _i, _i]),
+    "selftok_manifold_count_nn_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "selftok_kid_sums_f32_workspace_bytes": (_sz, [_i, _i, _i]),
+    "selftok_kid_sums_f32": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
 }
 
 

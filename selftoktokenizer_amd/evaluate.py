@@ -200,26 +200,42 @@ def folder_loader(paths: Sequence[str], size: int, device=None, preprocess: str 
 
 
 COMPARE_METRICS = ("fid", "is", "precision", "recall")
+COMPARE_METRICS_EXTRA = ("kid", "density", "coverage")
 
 
 def compare_sets(load_ref: Callable[[int, int], torch.Tensor], n_ref: int, load_gen: Callable[[int, int], torch.Tensor], n_gen: int, fid=None,
-                 metrics: Sequence[str] = COMPARE_METRICS, batch: int = 64, k: Optional[int] = None, split_size: Optional[int] = None, device=None) -> Dict:
+                 metrics: Sequence[str] = COMPARE_METRICS, batch: int = 64, k: Optional[int] = None, split_size: Optional[int] = None, device=None,
+                 kid_subsets: Optional[int] = None, kid_subset_size: Optional[int] = None, kid_seed: Optional[int] = None, nearest: bool = False) -> Dict:
     """Two image sets against each other, the figures of the ADM / LlamaGen protocol that this project defines: FID, Inception Score (of the generated set),
     improved precision and recall.  load_ref(lo, hi) / load_gen(lo, hi) -> float tensor [hi - lo, 3, H, W] in [-1, 1] (host or device; load_gen may decode
     token ids through a pipeline); each rank walks its contiguous shard (dist.shard_range) of either set in batches of `batch`, the pool3 features (and, for
     "is", the fc logits) are gathered to every rank and every figure is taken of the GATHERED matrices, so it does not depend on the sharding or the batch.
     `fid`: a fid.InceptionNet (no default network: the weights are not shipped), built with logits=True when "is" is asked for.  k: neighbours of
-    precision / recall (default 3); split_size: rows per Inception Score split (default 5000)."""
+    precision / recall (default 3); split_size: rows per Inception Score split (default 5000).
+    COMPARE_METRICS_EXTRA, on the same gathered features (genmetrics.GEN_METRICS_DEFINITION): "kid" (kid_subsets subsets of kid_subset_size rows drawn with
+    kid_seed, defaults 100 x 1000, seed 2020: the unbiased figure for sets too small for FID) gives `kid`, `kid_std` and the three parameters; "density" and
+    "coverage" give the fractions and `density_count` / `coverage_count`, with the k and the reference radii of precision (computed once per call; asked for
+    together with density, precision is count > 0, the membership entry's bits).  nearest=True: out["nearest"] = {"index", "d2"}, for every generated image
+    its nearest reference image by squared pool3 distance."""
     from . import fid as FD, genmetrics as GM
     metrics = tuple(metrics)
-    bad = [m for m in metrics if m not in COMPARE_METRICS]
+    bad = [m for m in metrics if m not in COMPARE_METRICS + COMPARE_METRICS_EXTRA]
     if bad or not metrics:
-        raise ValueError(f"metrics {metrics!r}: expected a non-empty subset of {COMPARE_METRICS}")
+        raise ValueError(f"metrics {metrics!r}: expected a non-empty subset of {COMPARE_METRICS + COMPARE_METRICS_EXTRA}")
     if fid is None:
         raise ValueError("compare_sets needs fid=<InceptionNet> (the weights are not shipped, so there is no default network)")
     k = GM.K_DEFAULT if k is None else int(k)
     split_size = GM.SPLIT_SIZE if split_size is None else int(split_size)
     with_is, with_pr = "is" in metrics, "precision" in metrics or "recall" in metrics
+    with_kid, with_dc = "kid" in metrics, "density" in metrics or "coverage" in metrics
+    kid_subsets = GM.KID_SUBSETS if kid_subsets is None else int(kid_subsets)
+    kid_subset_size = GM.KID_SUBSET_SIZE if kid_subset_size is None else int(kid_subset_size)
+    kid_seed = GM.KID_SEED if kid_seed is None else int(kid_seed)
+    if with_kid and (kid_subsets < 1 or kid_subset_size < 2 or kid_subset_size > min(n_ref, n_gen)):
+        raise ValueError(f"'kid' needs kid_subsets >= 1 and 2 <= kid_subset_size <= min(n_ref, n_gen), got {kid_subsets} subsets of {kid_subset_size} rows, "
+                         f"{n_ref} and {n_gen} images")
+    if with_dc and (n_ref <= k or not 1 <= k <= GM.K_MAX):
+        raise ValueError(f"'density' / 'coverage' need 1 <= k <= {GM.K_MAX} and more than k reference images, got k {k}, {n_ref} images")
     if with_is and fid.fc_packed is None:
         raise ValueError("compare_sets: 'is' needs a network built with logits=True")
     if "fid" in metrics and min(n_ref, n_gen) < 2:
@@ -254,10 +270,39 @@ def compare_sets(load_ref: Callable[[int, int], torch.Tensor], n_ref: int, load_
     if with_is:
         out["is"] = GM.inception_score(lg, split_size)
         out["split_size"] = split_size
-    if with_pr:
+    if with_pr and not with_dc:
         pr = GM.precision_recall(fr, fg, k)
         out.update({key: v for key, v in pr.items() if key.split("_")[0] in metrics or key == "k"})
-    if with_is or with_pr:
+    nn = None
+    if with_dc:                                                   # one set of reference radii serves precision, density and coverage
+        r2_ref = GM.knn_radii(fr, k)
+        pr = {}
+        if "density" in metrics:
+            count, nn_d2, nn_idx = GM.ball_counts(fg, fr, r2_ref)
+            nn = (nn_idx, nn_d2)
+            dc = int(count.sum(dtype=torch.int64).item())
+            pr.update({"density": dc / (k * n_gen), "density_count": dc})
+            if "precision" in metrics:                            # count > 0 is the membership entry bit for bit
+                pc = int((count > 0).sum().item())
+                pr.update({"precision": pc / n_gen, "precision_count": pc})
+        elif "precision" in metrics:
+            pc = int(GM.manifold_members(fg, fr, r2_ref).sum().item())
+            pr.update({"precision": pc / n_gen, "precision_count": pc})
+        if "recall" in metrics:
+            rc = int(GM.manifold_members(fr, fg, GM.knn_radii(fg, k)).sum().item())
+            pr.update({"recall": rc / n_ref, "recall_count": rc})
+        if "coverage" in metrics:
+            cc = GM.coverage_count(fr, fg, r2_ref)
+            pr.update({"coverage": cc / n_ref, "coverage_count": cc})
+        order = ("precision", "recall", "density", "coverage", "precision_count", "recall_count", "density_count", "coverage_count")
+        out.update({key: pr[key] for key in order if key in pr})
+        out["k"] = k
+    if with_kid:
+        out.update(GM.kid(fr, fg, kid_subsets, kid_subset_size, kid_seed))
+    if nearest:
+        nn_idx, nn_d2 = GM.nearest_neighbours(fg, fr) if nn is None else nn
+        out["nearest"] = {"index": [int(v) for v in nn_idx.cpu().numpy()], "d2": [float(v) for v in nn_d2.cpu().numpy()]}
+    if with_is or with_pr or with_dc or with_kid or nearest:
         definition["gen_metrics"] = GM.GEN_METRICS_DEFINITION
     out["metric_definition"] = definition
     return out

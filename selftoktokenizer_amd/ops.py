@@ -1614,3 +1614,57 @@ def is_kl_rows(logits: torch.Tensor, colmean: torch.Tensor, split_size: int, wor
     out = torch.empty(N, dtype=torch.float64, device=logits.device)
     _lib.check(lib.selftok_is_kl_rows(_p(logits), _p(colmean), _p(out), _p(ws), ws.numel() * ws.element_size(), N, C, int(split_size), _stream()), "selftok_is_kl_rows")
     return out
+
+
+# ---- density / coverage, nearest neighbours, KID (csrc/gen_metrics_kdc.hip): ball counts and the nearest set row per query, the polynomial-kernel sums ----
+def manifold_count_nn(x: torch.Tensor, a: torch.Tensor, r2: Optional[torch.Tensor] = None, *, split: int = 0, out_count: Optional[torch.Tensor] = None,
+                      out_d2: Optional[torch.Tensor] = None, out_idx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """x [M, D], a [N, D] fp32, r2 [N] fp32 or None -> (count int32 [M] | None, nn_d2 fp32 [M], nn_idx int32 [M]): count[i] = the number of j with
+    d2(x_i, a_j) <= r2[j] (None without radii), nn_d2[i] = the smallest non-NaN d2(x_i, a_j) and nn_idx[i] the lowest j that has it (NaN / -1 when there is none).
+    The M x N matrix is never stored; the d2 bits are manifold_member's.  split: launch-shape override, never visible in the result.  M == 0: empty tensors, no launch."""
+    x, a = _gm_rows("manifold_count_nn", x), _gm_rows("manifold_count_nn", a)
+    _need_cuda(x, a, r2, out_count, out_d2, out_idx, workspace)
+    M, D = x.shape
+    N = a.shape[0]
+    if a.shape[1] != D or (r2 is not None and (r2.dtype != torch.float32 or tuple(r2.shape) != (N,))):
+        raise _lib.SelftokHipError(f"manifold_count_nn: expected x [M, D], a [N, D] and a float32 r2 [N] or None, got {tuple(x.shape)}, {tuple(a.shape)}, "
+                                   f"{None if r2 is None else (r2.dtype, tuple(r2.shape))}")
+    if r2 is None and out_count is not None:
+        raise _lib.SelftokHipError("manifold_count_nn: `out_count` without r2 (no radii, no count)")
+    r2 = None if r2 is None else r2.contiguous()
+    lib = _lib.load()
+    ws = _gm_workspace("selftok_manifold_count_nn_f32_workspace_bytes", lib.selftok_manifold_count_nn_f32_workspace_bytes(M, N, D), x.device, workspace)
+    outs = []
+    for name, t, dtype, want in (("out_count", out_count, torch.int32, r2 is not None), ("out_d2", out_d2, torch.float32, True), ("out_idx", out_idx, torch.int32, True)):
+        if not want:
+            outs.append(None)
+        elif t is None:
+            outs.append(torch.empty(M, dtype=dtype, device=x.device))
+        elif t.dtype != dtype or tuple(t.shape) != (M,) or not t.is_contiguous():
+            raise _lib.SelftokHipError(f"manifold_count_nn: `{name}` must be a contiguous {dtype} [{M}], got {t.dtype} {tuple(t.shape)}")
+        else:
+            outs.append(t)
+    count, d2, idx = outs
+    if M:
+        _lib.check(lib.selftok_manifold_count_nn_f32(_p(x), _p(a), _p(r2), _p(count), _p(d2), _p(idx), _p(ws), ws.numel() * ws.element_size(), M, N, D, int(split), _stream()),
+                   "selftok_manifold_count_nn_f32")
+    return count, d2, idx
+
+
+def kid_sums(xs: torch.Tensor, ys: torch.Tensor, S: int, m: int, *, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """xs, ys [S * m, D] fp32: subset s is rows s * m .. s * m + m - 1 of either -> fp64 [S, 3] = (XX, YY, XY) of k(u, v) = (u.v / D + 1)^3, XX and YY without
+    the positions i == j.  A subset's triple depends on its own 2 m rows alone."""
+    xs, ys = _gm_rows("kid_sums", xs), _gm_rows("kid_sums", ys)
+    _need_cuda(xs, ys, out, workspace)
+    S, m = int(S), int(m)
+    D = xs.shape[1]
+    if tuple(xs.shape) != (S * m, D) or tuple(ys.shape) != (S * m, D) or S < 1:
+        raise _lib.SelftokHipError(f"kid_sums: expected xs and ys [S * m, D] = [{S * m}, D], got {tuple(xs.shape)} and {tuple(ys.shape)}")
+    lib = _lib.load()
+    ws = _gm_workspace("selftok_kid_sums_f32_workspace_bytes", lib.selftok_kid_sums_f32_workspace_bytes(S, m, D), xs.device, workspace)
+    if out is None:
+        out = torch.empty(S, 3, dtype=torch.float64, device=xs.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (S, 3) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"kid_sums: `out` must be a contiguous float64 [{S}, 3], got {out.dtype} {tuple(out.shape)}")
+    _lib.check(lib.selftok_kid_sums_f32(_p(xs), _p(ys), _p(out), _p(ws), ws.numel() * ws.element_size(), S, m, D, _stream()), "selftok_kid_sums_f32")
+    return out

@@ -10,7 +10,10 @@ With --tokens sequence i is decoded from the noise of a generator seeded --seed 
 the same bits for every batch size only with --gemm exact; the default fp32 sampler is not bit-reproducible across batch shapes.
 --ref / --samples: a folder of image files (searched recursively, sorted, pre-processed to --data_size like eval_psnr.py) or an ADM-style .npz whose arr_0
 is uint8 [N, H, W, 3].  Prints ONE JSON object on rank 0.  The figures are those of the published definitions on the weights given; nothing here is pinned
-against the ADM evaluator (unpinned), and sFID is not offered (genmetrics.py says why)."""
+against the ADM evaluator (unpinned), and sFID is not offered (genmetrics.py says why).
+--metrics also takes kid, density and coverage (evaluate.COMPARE_METRICS_EXTRA; unpinned against torch-fidelity and prdc): KID is the unbiased figure for sets
+of a few thousand images, where FID is biased.  --nn-out FILE.npz writes, for every generated image, the index of its nearest reference image and the squared
+pool3 distance to it (`index`, `d2`), and keeps both out of the JSON object."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -26,7 +29,11 @@ ap.add_argument("--synthetic", action="store_true", help="hash-generated Incepti
 ap.add_argument("--fid-weights", default=None, help="pytorch-fid's pt_inception-2015-12-05 state dict, with fc.weight / fc.bias for the Inception Score")
 ap.add_argument("--k", type=int, default=GM.K_DEFAULT, help="neighbours of precision / recall")
 ap.add_argument("--split-size", type=int, default=GM.SPLIT_SIZE, help="rows per Inception Score split")
-ap.add_argument("--metrics", default=",".join(E.COMPARE_METRICS))
+ap.add_argument("--metrics", default=",".join(E.COMPARE_METRICS), help="any of " + ", ".join(E.COMPARE_METRICS + E.COMPARE_METRICS_EXTRA))
+ap.add_argument("--kid-subsets", type=int, default=GM.KID_SUBSETS, help="subsets of the KID estimate")
+ap.add_argument("--kid-subset-size", type=int, default=GM.KID_SUBSET_SIZE, help="rows of either set per KID subset")
+ap.add_argument("--kid-seed", type=int, default=GM.KID_SEED, help="seed of the KID subset draw")
+ap.add_argument("--nn-out", default=None, help="FILE.npz: the nearest reference image of every generated image (index, d2), rank 0")
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--data_size", type=int, default=256)
 ap.add_argument("--preprocess", default="adm", choices=["reference", "bicubic", "adm"], help="how files of a folder become data_size x data_size images")
@@ -81,9 +88,14 @@ if a.tokens:
 else:
     load_gen, n_gen, src_gen = image_set(a.samples)
 
-res = E.compare_sets(load_ref, n_ref, load_gen, n_gen, fid=net, metrics=metrics, batch=a.batch, k=a.k, split_size=a.split_size, device=dev)
+res = E.compare_sets(load_ref, n_ref, load_gen, n_gen, fid=net, metrics=metrics, batch=a.batch, k=a.k, split_size=a.split_size, device=dev,
+                     kid_subsets=a.kid_subsets, kid_subset_size=a.kid_subset_size, kid_seed=a.kid_seed, nearest=a.nn_out is not None)
 D.barrier()
+nn = res.pop("nearest", None)
 if rank == 0:
+    if a.nn_out:
+        np.savez(a.nn_out, index=np.asarray(nn["index"], np.int32), d2=np.asarray(nn["d2"], np.float32))
+        res["nn_out"] = a.nn_out
     line = {"tool": "eval_generated", "ref": src_ref, "samples": src_gen, "fid_weights": net.source, "pinned": GM.GEN_METRICS_DEFINITION["pinned"], **res}
     print(json.dumps(line), flush=True)
     if a.out:
