@@ -254,13 +254,24 @@ int selftok_clamp01_bf16(void* img, long n, hipStream_t stream);
  *   residual: out = bf16(bf16(conv + bias) + residual), the two roundings of `x + h` (ResnetBlock.forward :262).
  * Weights: the checkpoint's [Cout, Cin, k, k] bf16 tensor packed once by selftok_conv2d_pack_weight_bf16 into an opaque image of
  * selftok_conv2d_packed_bytes(Cout, Cin, ksize, bn) bytes; bn = output channels per workgroup, 128 (Cout >= 64) or 32 (narrow
- * outputs: encoder conv_out, decoder conv_out); the same bn must be passed to the convolution. */
+ * outputs: encoder conv_out, decoder conv_out); the same bn must be passed to the convolution.  The image holds ceil(Cout / bn)
+ * channel blocks of ceil(Cin / 32) input blocks each, zero padded: [channel block][input block][tap][bn][32].
+ * Refused with SELFTOK_EINVAL, before anything is launched or written (both builds, one message):
+ *   - Cstore that opens a channel block the image does not hold: need ceil(Cstore / bn) == ceil(Cout / bn).  Stored zero channels may
+ *     pad the last block (Cout = 100, Cstore = 128), never start a new one (Cout = 128, Cstore = 132; Cout = 100, Cstore = 256);
+ *   - an empty stride-2 output: stride 2 with H or W below 2 (Ho or Wo would be 0).
+ * Two preconditions the entry cannot check:
+ *   - (Cin + 31) / 32 of the call must equal that of the Cin the image was packed with (x may store more channels than the layer has,
+ *     conv_in: 3 as 8, within the same count of 32-blocks);
+ *   - stored channels of x at or above the packed Cin must be finite: they meet zero weights, and NaN * 0 = NaN on both builds. */
 size_t selftok_conv2d_packed_bytes(int Cout, int Cin, int ksize, int bn);
 int selftok_conv2d_pack_weight_bf16(const void* w, void* packed, int Cout, int Cin, int ksize, int bn, hipStream_t stream);
 int selftok_conv2d_nhwc_bf16(const void* x, const void* packed, const void* bias, const void* residual, void* out, int B, int H, int W, int Cin, int Cout,
                              int Cstore, int ldo, int ksize, int stride, int upsample, int bn, hipStream_t stream);
-/* GroupNorm(groups, eps, affine) [+ SiLU] on [B, HW, C] bf16 (channels-last): selftok_groupnorm_silu_bf16's arithmetic, statistics
- * accumulated in fp64 and reduced in a fixed order (deterministic).  C / 8 must divide 256, (C / groups) % 4 == 0. */
+/* GroupNorm(groups, eps, affine) [+ SiLU] on [B, HW, C] bf16 (channels-last): statistics accumulated in fp64 and reduced in a fixed
+ * order (deterministic), (x - mean) * rstd * w + b evaluated in fp64 and rounded ONCE to bf16 (every element is the correctly rounded
+ * value or its neighbour, also where the product and the bias cancel), SiLU in fp32 on that bf16 value as selftok_groupnorm_silu_bf16.
+ * C / 8 must divide 256, (C / groups) % 4 == 0. */
 size_t selftok_groupnorm_nhwc_workspace_bytes(int B, int HW, int C);
 int selftok_groupnorm_silu_nhwc_bf16(const void* x, const void* weight, const void* bias, void* out, void* workspace, int B, int HW, int C, int groups,
                                      float eps, int apply_silu, hipStream_t stream);

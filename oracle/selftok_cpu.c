@@ -813,6 +813,11 @@ int selftok_conv2d_nhwc_bf16(const void* xv, const void* pv, const void* bv, con
         (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || (ksize == 1 && stride != 1) || (upsample != 0 && upsample != 1) || (bn != 32 && bn != 128) ||
         (upsample && stride != 1) || (stride == 2 && bn != 128))
         return fail("conv2d_nhwc_bf16: bad argument (Cin % 8, Cstore % 4, ldo % 4, ksize 1|3, stride 1|2 (3x3 only), bn 32|128)");
+    /* the GPU library's two further refusals (csrc/conv.hip): same conditions, same messages, nothing written */
+    if ((Cstore + bn - 1) / bn > (Cout + bn - 1) / bn)
+        return fail("conv2d_nhwc_bf16: Cstore opens a channel block of bn the packed image does not hold (need ceil(Cstore / bn) == ceil(Cout / bn))");
+    if (stride == 2 && (((H << upsample) >> 1) == 0 || ((W << upsample) >> 1) == 0))
+        return fail("conv2d_nhwc_bf16: empty stride-2 output (H or W below 2)");
     const uint16_t *x = (const uint16_t*)xv, *pk = (const uint16_t*)pv, *bias = (const uint16_t*)bv, *res = (const uint16_t*)rv;
     uint16_t* out = (uint16_t*)ov;
     const int taps = ksize * ksize, ncb = (Cin + 31) / 32, Hi = H << upsample, Wi = W << upsample;
@@ -843,6 +848,20 @@ size_t selftok_groupnorm_nhwc_workspace_bytes(int B, int HW, int C)
     if (B <= 0 || HW <= 0 || C <= 0) return 0;
     return (size_t)B * 32 * (C / 4) * 2 * sizeof(double) + (size_t)B * 64 * 2 * sizeof(float) + 256;
 }
+/* fp64 -> bf16 in ONE rounding to nearest even: through fp32 rounded to odd (csrc/conv.hip d2bf) */
+static inline uint16_t d2bf(double d)
+{
+    float f = (float)d;
+    const double back = (double)f;
+    if (back != d && d == d) {
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        if (fabs(back) > fabs(d)) u -= 1;
+        u |= 1u;
+        memcpy(&f, &u, 4);
+    }
+    return f2bf(f);
+}
 int selftok_groupnorm_silu_nhwc_bf16(const void* xv, const void* wv, const void* bv, void* ov, void* workspace, int B, int HW, int C, int groups,
                                      float eps, int apply_silu, hipStream_t s)
 {
@@ -855,24 +874,23 @@ int selftok_groupnorm_silu_nhwc_bf16(const void* xv, const void* wv, const void*
 #pragma omp parallel for schedule(static)
     for (int b = 0; b < B; ++b) {
         double s1[64] = {0}, s2[64] = {0};
-        float meanf[64], rstd[64];
+        double mean[64], rstd[64];
         for (int p = 0; p < HW; ++p) {                         /* one pass over the sample, pixel-major (the layout's order) */
             const uint16_t* xp = x + ((size_t)b * HW + p) * C;
             for (int c = 0; c < C; ++c) { const double d = bf2f(xp[c]); s1[c / cpg] += d; s2[c / cpg] += d * d; }
         }
         for (int g = 0; g < groups; ++g) {
-            const double n = (double)HW * cpg, mean = s1[g] / n;
-            double var = s2[g] / n - mean * mean;
+            const double n = (double)HW * cpg;
+            mean[g] = s1[g] / n;
+            double var = s2[g] / n - mean[g] * mean[g];
             if (var < 0) var = 0;
-            meanf[g] = (float)mean;
-            const float varf = (float)(var + (mean - (double)meanf[g]) * (mean - (double)meanf[g]));
-            rstd[g] = 1.0f / sqrtf(varf + eps);
+            rstd[g] = 1.0 / sqrt(var + (double)eps);
         }
-        for (int p = 0; p < HW; ++p) for (int c = 0; c < C; ++c) {
+        for (int p = 0; p < HW; ++p) for (int c = 0; c < C; ++c) {         /* fp64, ONE rounding to bf16 (csrc/conv.hip); SiLU in fp32 on the bf16 value */
             const size_t i = ((size_t)b * HW + p) * C + c;
-            float y = rbf((bf2f(x[i]) - meanf[c / cpg]) * rstd[c / cpg] * bf2f(w[c]) + bf2f(bb[c]));
-            if (apply_silu) y = y / (1.0f + expf(-y));
-            out[i] = f2bf(y);
+            uint16_t r = d2bf(((double)bf2f(x[i]) - mean[c / cpg]) * (rstd[c / cpg] * (double)bf2f(w[c])) + (double)bf2f(bb[c]));
+            if (apply_silu) { const float y = bf2f(r); r = f2bf(y / (1.0f + expf(-y))); }
+            out[i] = r;
         }
     }
     return SELFTOK_OK;

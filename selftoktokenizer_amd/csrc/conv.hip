@@ -29,9 +29,9 @@
 //     accumulator quad, i.e. 8-byte NHWC stores straight from the accumulators;
 //   * epilogue: + bias in fp32, one rounding to bf16; optional residual `x + h` (ResnetBlock.forward :262) with the reference's second
 //     rounding: bf16(bf16(acc + bias) + res).
-// GroupNorm(32 groups) + SiLU for the same layout: statistics in fp64 (sum and sum of squares of bf16 values are exact to 1e-16, so
-// mean / variance are the correctly rounded fp32 values regardless of the summation order: deterministic, partials reduced in a fixed
-// order), applied with the arithmetic of groupnorm_silu_bf16_kernel (vae.hip).
+// GroupNorm(32 groups) + SiLU for the same layout: statistics in fp64 (sum and sum of squares of bf16 values are exact to 1e-16:
+// deterministic, partials reduced in a fixed order), the normalisation evaluated in fp64 and rounded once to bf16, SiLU in fp32 on that
+// bf16 value as groupnorm_silu_bf16_kernel (vae.hip) does.
 #include "common.h"
 #include "selftok_hip.h"
 #include <stdlib.h>
@@ -494,8 +494,9 @@ __global__ __launch_bounds__(256) void gn_nhwc_partial_kernel(const uint16_t* __
     }
 }
 
-// pass 2: stats[b][g] = (mean, rstd) in fp32 from the fp64 sums
-__global__ void gn_nhwc_finalize_kernel(const double* __restrict__ part, float2* __restrict__ stats, int HW, int C, int groups, int nblk, float eps)
+// pass 2: (mean, rstd) of every group in fp64 from the fp64 sums.  Thread gi alone reads and owns the partial sums of group gi's quads, so it
+// leaves its result in the first of them (pixel range 0, quad gi * qpg): the workspace keeps its size and no other thread meets that slot.
+__global__ void gn_nhwc_finalize_kernel(double* __restrict__ part, int HW, int C, int groups, int nblk, float eps)
 {
     const int b = blockIdx.x, gi = threadIdx.x;
     if (gi >= groups) return;
@@ -508,26 +509,41 @@ __global__ void gn_nhwc_finalize_kernel(const double* __restrict__ part, float2*
         }
     const double n = (double)HW * cpg;
     const double mean = s / n;
-    const double var = fmax(q / n - mean * mean, 0.0);
-    const float meanf = (float)mean;
-    // the reference (and groupnorm_silu_bf16_kernel) centre on the fp32 mean: var about meanf = var + (mean - meanf)^2
-    const float varf = (float)(var + (mean - (double)meanf) * (mean - (double)meanf));
-    stats[b * groups + gi] = make_float2(meanf, 1.0f / __builtin_sqrtf(varf + eps));
+    const double var = fmax(q / n - mean * mean, 0.0);      // sums of bf16 values and of their squares are exact to 1e-16: no cancellation that shows
+    double* o = part + ((size_t)b * nblk * (C >> 2) + gi * qpg) * 2;
+    o[0] = mean; o[1] = 1.0 / __builtin_sqrt(var + (double)eps);
 }
 
-// pass 3: y = bf16((x - mean) * rstd * w + b) [SiLU on the bf16 value] -- the arithmetic of vae.hip.  256 % (C / 8) == 0, so a thread
-// meets the same 8 channels in every iteration of its grid-stride loop: their statistics and affine parameters stay in registers.
+// fp64 -> bf16 in ONE rounding to nearest even: through fp32 rounded to odd (the inexact bit is kept as the last of 16 spare bits).
+// Cutting that fp32 from the bits of the double instead of converting there and back was measured and is slower (0.44 vs 0.40 ms on
+// 16 x 102400 x 128).
+__device__ __forceinline__ uint16_t d2bf(double d)
+{
+    float f = (float)d;
+    const double back = (double)f;
+    if (back != d && d == d) {
+        uint32_t u = __float_as_uint(f);
+        if (__builtin_fabs(back) > __builtin_fabs(d)) u -= 1;      // towards zero
+        f = __uint_as_float(u | 1u);
+    }
+    return f2bf(f);
+}
+
+// pass 3: y = bf16((x - mean) * rstd * w + b) evaluated in fp64 and rounded ONCE [SiLU in fp32 on the bf16 value, as vae.hip] -- an fp32
+// evaluation is several bf16 ulps off where the product and the bias cancel (tests/test_conv_edges_gpu.py); the pass stays memory bound.
+// 256 % (C / 8) == 0, so a thread meets the same 8 channels in every iteration of its grid-stride loop: their statistics and affine
+// parameters stay in registers.
 __global__ __launch_bounds__(256) void gn_nhwc_apply_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, const uint16_t* __restrict__ bias,
-                                                            const float2* __restrict__ stats, uint16_t* __restrict__ out, int C, int groups, int apply_silu, long chunks)
+                                                            const double* __restrict__ part, uint16_t* __restrict__ out, int C, int groups, int nblk, int apply_silu, long chunks)
 {
     const int cpp = C >> 3, cpg = C / groups;
     const int b = blockIdx.y, chunk = threadIdx.x % cpp;
-    float mean[8], rstd[8], ww[8], bb[8];
+    double mean[8], sc[8], bb[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int ch = chunk * 8 + e;
-        const float2 st = stats[b * groups + ch / cpg];
-        mean[e] = st.x; rstd[e] = st.y; ww[e] = bf2f(w[ch]); bb[e] = bf2f(bias[ch]);
+        const double* st = part + ((size_t)b * nblk * (C >> 2) + (ch / cpg) * (cpg >> 2)) * 2;
+        mean[e] = st[0]; sc[e] = st[1] * (double)bf2f(w[ch]); bb[e] = (double)bf2f(bias[ch]);
     }
     const uint4* __restrict__ xp = reinterpret_cast<const uint4*>(x) + (size_t)b * chunks;
     uint4* __restrict__ op = reinterpret_cast<uint4*>(out) + (size_t)b * chunks;
@@ -541,9 +557,8 @@ __global__ __launch_bounds__(256) void gn_nhwc_apply_kernel(const uint16_t* __re
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int e = 2 * k + h;
-                float y = rbf((bf2f((uint16_t)(in[k] >> (16 * h))) - mean[e]) * rstd[e] * ww[e] + bb[e]);
-                if (apply_silu) y = y / (1.0f + expf(-y));
-                r2[h] = f2bf(y);
+                r2[h] = d2bf(((double)bf2f((uint16_t)(in[k] >> (16 * h))) - mean[e]) * sc[e] + bb[e]);
+                if (apply_silu) { const float y = bf2f(r2[h]); r2[h] = f2bf(y / (1.0f + expf(-y))); }
             }
             o[k] = (uint32_t)r2[0] | ((uint32_t)r2[1] << 16);
         }
@@ -602,6 +617,16 @@ int selftok_conv2d_nhwc_bf16(const void* x, const void* packed, const void* bias
         set_last_error("conv2d_nhwc_bf16: bad argument (Cin % 8, Cstore % 4, ldo % 4, ksize 1|3, stride 1|2 (3x3 only), bn 32|128)");
         return SELFTOK_EINVAL;
     }
+    // Every launch below has ceil(Cstore / bn) channel blocks in gridDim.y and each reads ITS block of the packed image, which holds only
+    // ceil(Cout / bn) of them: stored zero channels may pad the last block, never open a new one.  Refused before anything is launched.
+    if ((Cstore + bn - 1) / bn > (Cout + bn - 1) / bn) {
+        set_last_error("conv2d_nhwc_bf16: Cstore opens a channel block of bn the packed image does not hold (need ceil(Cstore / bn) == ceil(Cout / bn))");
+        return SELFTOK_EINVAL;
+    }
+    if (stride == 2 && (((H << upsample) >> 1) == 0 || ((W << upsample) >> 1) == 0)) {
+        set_last_error("conv2d_nhwc_bf16: empty stride-2 output (H or W below 2)");
+        return SELFTOK_EINVAL;
+    }
     if (B == 0) return SELFTOK_OK;
     ConvParams P;
     P.x = (const uint16_t*)x; P.w = (const uint16_t*)packed; P.bias = (const uint16_t*)bias; P.res = (const uint16_t*)residual; P.out = (uint16_t*)out;
@@ -657,16 +682,15 @@ int selftok_groupnorm_silu_nhwc_bf16(const void* x, const void* weight, const vo
     }
     if (B == 0) return SELFTOK_OK;
     const int nblk = gn_nblk(HW);
-    double* part = (double*)workspace;
-    float2* stats = (float2*)((char*)workspace + (((size_t)B * nblk * (C / 4) * 2 * sizeof(double) + 255) & ~(size_t)255));
+    double* part = (double*)workspace;                                        // [B][nblk][C / 4][2] partial sums; the rest of the workspace is not used
     hipLaunchKernelGGL(gn_nhwc_partial_kernel, dim3(nblk, B), dim3(256), 0, stream, (const uint16_t*)x, part, HW, C, nblk);
-    hipLaunchKernelGGL(gn_nhwc_finalize_kernel, dim3(B), dim3(64), 0, stream, (const double*)part, stats, HW, C, groups, nblk, eps);
+    hipLaunchKernelGGL(gn_nhwc_finalize_kernel, dim3(B), dim3(64), 0, stream, part, HW, C, groups, nblk, eps);
     const long chunks = (long)HW * (C >> 3);                                  // per sample
     long blocks = (chunks + 255) / 256;
     const long cap = (256l * 16 + B - 1) / B;                                 // ~16 workgroups per CU over the whole batch
     if (blocks > cap) blocks = cap < 1 ? 1 : cap;
     hipLaunchKernelGGL(gn_nhwc_apply_kernel, dim3((unsigned)blocks, B), dim3(256), 0, stream, (const uint16_t*)x, (const uint16_t*)weight, (const uint16_t*)bias,
-                       (const float2*)stats, (uint16_t*)out, C, groups, apply_silu, chunks);
+                       (const double*)part, (uint16_t*)out, C, groups, nblk, apply_silu, chunks);
     return check_launch("groupnorm_silu_nhwc");
 }
 

@@ -717,6 +717,8 @@ def conv2d_nhwc(x: torch.Tensor, pc: PackedConv, stride: int = 1, upsample: bool
     B, H, W, Cin = x.shape
     assert Cin % 8 == 0 and (Cin + 31) // 32 == (pc.cin + 31) // 32 and Cin >= pc.cin, (Cin, pc.cin)
     cs = (pc.cout + 3) // 4 * 4 if cstore is None else cstore
+    # stored zero channels may pad the last channel block of the packed image, never open a block it does not hold (include/selftok_hip.h)
+    assert cs % 4 == 0 and cs >= pc.cout and (cs + pc.bn - 1) // pc.bn == (pc.cout + pc.bn - 1) // pc.bn, (cs, pc.cout, pc.bn)
     Hi, Wi = (H * 2, W * 2) if upsample else (H, W)
     Ho, Wo = (Hi // 2, Wi // 2) if stride == 2 else (Hi, Wi)
     out = torch.empty(B, Ho, Wo, cs, dtype=torch.bfloat16, device=x.device)
