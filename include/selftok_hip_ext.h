@@ -234,6 +234,35 @@ size_t selftok_lpips_distance_workspace_bytes(int B, int npix);
 int selftok_lpips_distance(const float* feat, const float* w, double* out, void* workspace, size_t workspace_bytes, int B, int npix, int C,
                            int accumulate, hipStream_t stream);
 
+/* ---- LPIPS on the VGG16 backbone: the 2 x 2 max-pool (csrc/lpips_vgg.hip) -----------------------------------------
+ * lpips.py's LPIPS_VGG_DEFINITION states the metric.  The 13 convolutions (3 x 3, pad 1, stride 1, ReLU) run on selftok_lpips_conv2d_f32
+ * and the input and distance stages are the ones above; the only stage VGG16 adds is torchvision's MaxPool2d with kernel 2 and stride 2:
+ * 2 x 2 windows, stride 2, no padding, floor mode: [N, H, W, C] -> [N, H / 2, W / 2, C], the last row / column of an odd map is dropped;
+ * a NaN in a window is the window's result.  H, W >= 2, N * H * W * C < 2^31; refusals are decided on the host before any launch. */
+int selftok_lpips_maxpool2s2_f32(const float* in, float* out, int N, int H, int W, int C, hipStream_t stream);
+
+/* ---- SSIM with a caller-chosen window and moment convention (csrc/image_ssim.hip) ------------------------------------
+ * recon [B, 3, H, W] in [0, 1] and orig [B, 3, H, W] as selftok_img_metrics takes them (bf16 or fp32 each; orig_signed != 0: the original is
+ * in [-1, 1]) -> out[B] fp64 on the device: the mean SSIM of each image over the three channels and the (H - taps + 1) x (W - taps + 1)
+ * "valid" windows -- what scikit-image's crop by (taps - 1) / 2 of its reflect-padded map leaves.
+ * window_host: `taps` separable fp64 weights in host memory (copied into the launch), taps odd, 3 <= taps <= 11.
+ * cov_norm: 1.0 for population moments, taps^2 / (taps^2 - 1) for scikit-image's use_sample_covariance=True.
+ * signed_range == 0: operands on [0, 1], C1 = 0.01^2, C2 = 0.03^2, selftok_img_metrics' own operand expressions;
+ * signed_range != 0: operands on [-1, 1], data range R = 2, C1 = (0.01 R)^2, C2 = (0.03 R)^2: the reconstruction is 2 r - 1 in fp64, a signed
+ *   original is taken as it is, an unsigned one is 2 v - 1.  quantize != 0: both inputs first become the bytes of selftok_img_to_u8 (as in
+ *   selftok_img_metrics), the operand is byte / 255 or 2 * (byte / 255) - 1 in fp64.
+ * Arithmetic, fp64 and every operation rounded on its own: the five window filters (horizontal pass, then vertical, taps ascending) ux, uy,
+ *   uxx, uyy, uxy; vx = cov_norm * (uxx - ux * ux), vy likewise, vxy = cov_norm * (uxy - ux * uy);
+ *   S = ((2 ux uy + C1) * (2 vxy + C2)) / ((ux^2 + uy^2 + C1) * (vx + vy + C2)).  This is the fp64 form: scikit-image >= 0.19 computes float32
+ *   input in float32, which is not imitated; unpinned against the package.
+ * With the 11 Gaussian weights, cov_norm 1.0 and signed_range 0 the result is column 0 of selftok_img_metrics bit for bit (the same
+ * operations in the same order).  No atomics: out[b] is a function of image b alone; identical images give exactly 1.0.
+ * Limits: B >= 1, H, W >= taps, B * 3 * H * W < 2^31, 0 < cov_norm <= 2.  The workspace (one fp64 per tile) is sized by the query; 0 with
+ * selftok_last_error set on a refused shape or window.  Every refusal is decided on the host before any launch. */
+size_t selftok_img_ssim_workspace_bytes(int B, int H, int W, int taps);
+int selftok_img_ssim(const void* recon, int recon_bf16, const void* orig, int orig_bf16, int orig_signed, int quantize, const double* window_host, int taps,
+                     double cov_norm, int signed_range, double* out, void* workspace, size_t workspace_bytes, int B, int H, int W, hipStream_t stream);
+
 /* ---- rFID stages (FID InceptionV3, pool3): convolution into a channel slice, 3 x 3 pools, input stage with resize, spatial mean,
  *      fp64 statistics ----------------------------------------------------------------------------------------------
  * The kernels of selftoktokenizer_amd/fid.py (FID_DEFINITION states the metric; csrc/fid.hip states the arithmetic and every summation

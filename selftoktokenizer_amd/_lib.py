@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SELFTOK_HIP_LIB") or os.path.join(_HERE, "libselftok_hip.so")   # override: ablation builds (tools/)
 
-_vp, _i, _f, _sz, _l = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_long
+_vp, _i, _f, _sz, _l, _d = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_long, C.c_double
 
 # name -> (restype, argtypes); must list every symbol declared in include/selftok_hip.h
 SIGNATURES = {
@@ -112,6 +112,9 @@ EXT_SIGNATURES = {
     "selftok_lpips_input": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "selftok_lpips_distance_workspace_bytes": (_sz, [_i, _i]),
     "selftok_lpips_distance": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "selftok_lpips_maxpool2s2_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "selftok_img_ssim_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "selftok_img_ssim": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "selftok_fid_conv2d_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp]),
     "selftok_fid_pool3_f32": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
     "selftok_fid_input": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -50,6 +50,22 @@ def ssim_window() -> np.ndarray:
     return np.ascontiguousarray(g / g.sum())
 
 
+def ssim_uniform_window(T: int = 7) -> np.ndarray:
+    """the T fp64 weights 1 / T of a uniform T x T window (T odd, 3 .. 11): scipy's uniform_filter, which skimage.metrics.structural_similarity applies by default
+    with T = 7"""
+    T = int(T)
+    if T % 2 == 0 or not 3 <= T <= 11:
+        raise ValueError(f"ssim_uniform_window: need an odd T, 3 <= T <= 11, got {T}")
+    return np.full(T, 1.0 / T, dtype=np.float64)
+
+
+def ssim_skimage_definition(signed: bool = True, quantize: bool = False) -> Dict:
+    """what "ssim_skimage" computes: skimage.metrics.structural_similarity's defaults (uniform 7 x 7 window, sample covariance, K1 = 0.01, K2 = 0.03), in fp64
+    (skimage >= 0.19 computes float32 input in float32; that path is not offered), on [-1, 1] data with data_range 2 or on [0, 1] data with data_range 1"""
+    return {"window": 7, "weights": "uniform", "K1": 0.01, "K2": 0.03, "data_range": 2.0 if signed else 1.0, "range": "[-1, 1]" if signed else "[0, 1]",
+            "covariance": "sample", "cov_norm": "49/48", "region": "valid", "precision": "float64", "on": "u8" if quantize else "float"}
+
+
 def psnr_of_mse(mse: np.ndarray) -> np.ndarray:
     with np.errstate(divide="ignore"):
         return 10.0 * np.log10(1.0 / np.asarray(mse, dtype=np.float64))
@@ -65,7 +81,7 @@ def metrics_each(recon: torch.Tensor, original: torch.Tensor, quantize: bool = F
 
 def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int, batch: int = 64, decoders: Sequence[str] = ("diffusion",),
              noise_fn: Optional[Callable[[int, int], torch.Tensor]] = None, seed: Optional[int] = 1234, renderer_pipe=None, verbose: bool = False,
-             metrics: Sequence[str] = ("psnr",), metrics_u8: bool = False, lpips=None, fid=None) -> Dict:
+             metrics: Sequence[str] = ("psnr",), metrics_u8: bool = False, lpips=None, fid=None, ssim_skimage_signed: bool = True) -> Dict:
     """PSNR of `n_images` images through `pipe` (and `renderer_pipe` for the one-step decoder), this rank's contiguous shard of them
     (dist.shard_range) in batches of `batch`; per-image values are gathered to every rank (one all_gather_into_tensor per decoder at the end).
     load_batch(lo, hi) -> float tensor [hi-lo, 3, H, W] in [-1, 1] (host or device).  noise_fn(lo, hi) -> [hi-lo, 16, h, w] replaces the
@@ -81,11 +97,23 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     and the figure is only comparable at the same N); `metric_definition["rfid"]` states the definition and the weights' source; metrics_u8 applies.
     "precision_recall" with `fid=` likewise: improved precision / recall (genmetrics.GEN_METRICS_DEFINITION, k = 3) on the same gathered pool3 features, the
     originals as the reference set against every decoder's reconstructions; every decoder's dict gains `precision`, `recall` and their integer counts, and
-    `metric_definition["precision_recall"]` states the definition.  Needs more than 3 images."""
+    `metric_definition["precision_recall"]` states the definition.  Needs more than 3 images.
+    "ssim_skimage": skimage.metrics.structural_similarity's defaults (ops.image_ssim's "skimage" preset: uniform 7 x 7 window, sample covariance, fp64) on the
+    device route; ssim_skimage_signed: on [-1, 1] data with data_range 2 (default) or on [0, 1] data with data_range 1.  Every decoder's dict gains
+    `ssim_skimage_mean` / `ssim_skimage_each`, `metric_definition["ssim_skimage"]` states window, moments, range and quantisation; metrics_u8 applies.
+    `lpips=` may also be a sequence of LpipsNets of different backbones: each then writes `lpips_<net>_mean` / `lpips_<net>_each` and
+    `metric_definition["lpips_<net>"]`; one network given on its own writes the `lpips_*` keys above."""
+    lpips_nets = None                                        # a sequence of networks: keys by backbone name
+    if lpips is not None and not callable(lpips):
+        lpips_nets = list(lpips)
+        names = [getattr(n, "net", None) for n in lpips_nets]
+        if not lpips_nets or None in names or len(set(names)) != len(names):
+            raise ValueError(f"lpips=: expected one LpipsNet or a non-empty sequence of LpipsNets of different backbones, got backbones {names}")
     with_lpips = "lpips" in metrics and lpips is not None
+    with_sk = "ssim_skimage" in metrics
     with_fid = "rfid" in metrics and fid is not None
     with_pr = "precision_recall" in metrics and fid is not None
-    bad = [m for m in metrics if m not in ("psnr", "ssim") and not (m == "lpips" and with_lpips) and not (m == "rfid" and with_fid) and not (m == "precision_recall" and with_pr)]
+    bad = [m for m in metrics if m not in ("psnr", "ssim", "ssim_skimage") and not (m == "lpips" and with_lpips) and not (m == "rfid" and with_fid) and not (m == "precision_recall" and with_pr)]
     if bad or not metrics:
         raise ValueError(f"metrics {tuple(metrics)!r}: expected a non-empty subset of ('psnr', 'ssim')" + (", or 'lpips' together with lpips=<LpipsNet>" if "lpips" in bad else "")
                          + (", or 'rfid' together with fid=<InceptionNet>" if "rfid" in bad else "")
@@ -97,7 +125,7 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
         if n_images <= GM.K_DEFAULT:
             raise ValueError(f"'precision_recall' needs more than k = {GM.K_DEFAULT} images (a k-th neighbour), got {n_images}")
     with_feats = with_fid or with_pr
-    on_device = "ssim" in metrics or with_lpips or with_feats
+    on_device = "ssim" in metrics or with_sk or with_lpips or with_feats
     if metrics_u8 and not on_device:
         raise ValueError("metrics_u8 needs 'ssim' in `metrics` (the device route); the host PSNR route is the float one")
     world, rank = D.world_size(), D.rank()       # the dist module's view: sharding and the gather below must agree
@@ -106,6 +134,7 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     if seed is not None:
         torch.manual_seed(int(seed) + rank)
     vals = {d: [] for d in decoders}
+    extra = {d: {} for d in decoders}            # "ssim_skimage" and the networks of a sequence: key -> fp64 [b] per batch, on the device
     feats = {d: [] for d in decoders}            # "rfid": pool3 features [b, 2048] fp32 per batch, the originals under None
     feats[None] = []
     ids_all = []
@@ -128,8 +157,13 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
             if on_device:
                 from . import ops
                 m = ops.image_metrics(rec.detach(), imgs, original_signed=True, quantize=metrics_u8)      # [b, 2] fp64, stays on the device
-                if with_lpips:
+                if with_lpips and lpips_nets is None:
                     m = torch.cat([m, lpips(rec.detach(), imgs, original_signed=True, quantize=metrics_u8)[:, None]], dim=1)      # [b, 3]
+                if with_sk:
+                    extra[d].setdefault("ssim_skimage", []).append(ops.image_ssim(rec.detach(), imgs, "skimage", None, ssim_skimage_signed, True, metrics_u8))
+                if with_lpips and lpips_nets is not None:
+                    for one in lpips_nets:
+                        extra[d].setdefault("lpips_" + one.net, []).append(one(rec.detach(), imgs, original_signed=True, quantize=metrics_u8))
                 vals[d].append(m)
                 if with_feats:
                     feats[d].append(fid.pool3(rec.detach(), signed=False, quantize=metrics_u8))
@@ -151,13 +185,17 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
         mu0, sigma0 = (t.cpu().numpy() for t in FD.statistics(gathered(None)))
     for d in decoders:
         if on_device:
-            mine = torch.cat(vals[d]) if vals[d] else torch.zeros(0, 3 if with_lpips else 2, dtype=torch.float64, device=pipe.device)
+            mine = torch.cat(vals[d]) if vals[d] else torch.zeros(0, 3 if with_lpips and lpips_nets is None else 2, dtype=torch.float64, device=pipe.device)
             allv = D.all_gather_rows(mine, counts).cpu().numpy()
             ssim, psnr = allv[:, 0], psnr_of_mse(allv[:, 1])
             out[d] = {"psnr_mean_dB": float(psnr.mean()) if psnr.size else float("nan"), "psnr_each_dB": [round(float(v), 6) for v in psnr],
                       "ssim_mean": float(ssim.mean()) if ssim.size else float("nan"), "ssim_each": [round(float(v), 9) for v in ssim]}
-            if with_lpips:
+            if with_lpips and lpips_nets is None:
                 out[d].update({"lpips_mean": float(allv[:, 2].mean()) if ssim.size else float("nan"), "lpips_each": [round(float(v), 9) for v in allv[:, 2]]})
+            for key in (["ssim_skimage"] if with_sk else []) + (["lpips_" + one.net for one in lpips_nets] if with_lpips and lpips_nets is not None else []):
+                col = extra[d].get(key, [])
+                v = D.all_gather_rows((torch.cat(col) if col else torch.zeros(0, dtype=torch.float64, device=pipe.device))[:, None], counts).cpu().numpy()[:, 0]
+                out[d].update({key + "_mean": float(v.mean()) if v.size else float("nan"), key + "_each": [round(float(x), 9) for x in v]})
             if with_fid:
                 out[d].update({"rfid": FD.frechet_distance(*FD.statistics(gathered(d)), mu0, sigma0), "rfid_n": int(n_images), "rfid_rank_deficient": n_images <= FD.FEATURES})
             if with_pr:
@@ -168,9 +206,14 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
         out[d] = {"psnr_mean_dB": float(allv.mean()) if allv.size else float("nan"), "psnr_each_dB": [round(float(v), 6) for v in allv]}
     if on_device:
         out["metric_definition"] = dict(SSIM_DEFINITION, on="u8" if metrics_u8 else "float")
-        if with_lpips:
+        if with_sk:
+            out["metric_definition"]["ssim_skimage"] = ssim_skimage_definition(ssim_skimage_signed, metrics_u8)
+        if with_lpips and lpips_nets is None:
             from .lpips import LPIPS_DEFINITION
-            out["metric_definition"]["lpips"] = dict(LPIPS_DEFINITION, weights=lpips.source)
+            out["metric_definition"]["lpips"] = dict(getattr(lpips, "definition", LPIPS_DEFINITION), weights=lpips.source)
+        elif with_lpips:
+            for one in lpips_nets:
+                out["metric_definition"]["lpips_" + one.net] = dict(one.definition, weights=one.source)
         if with_fid:
             out["metric_definition"]["rfid"] = dict(FD.FID_DEFINITION, weights=fid.source, resized=bool(fid.resize))
         if with_pr:

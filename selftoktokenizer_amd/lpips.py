@@ -1,10 +1,11 @@
-"""LPIPS (Zhang et al. 2018), AlexNet backbone with the v0.1 linear layers -- `lpips.LPIPS()`'s default -- on the project's own kernels
-(csrc/lpips.hip): the value of an image pair is a function of that pair alone, bit for bit, whatever the batch around it.
+"""LPIPS (Zhang et al. 2018) with the v0.1 linear layers on the project's own kernels (csrc/lpips.hip, csrc/lpips_vgg.hip): the AlexNet backbone --
+`lpips.LPIPS()`'s default -- and the VGG16 backbone (`net="vgg"`).  The value of an image pair is a function of that pair alone, bit for bit,
+whatever the batch around it.
 
-LPIPS_DEFINITION states the metric; tests/lpips_cases.py restates it in torch-CPU fp64 / numpy.  The published weight files (torchvision's
-AlexNet, the `lpips` package's alex.pth) are read by `LpipsNet.from_files`; `LpipsNet.synthetic` builds the same architecture on
-hash-generated weights, which is what the tests run on.  The implementation is held to the published definition, not to the `lpips`
-package: unpinned against the package.
+LPIPS_DEFINITION / LPIPS_VGG_DEFINITION state the metric; tests/lpips_cases.py and tests/lpips_vgg_cases.py restate it in torch-CPU fp64 / numpy.
+The published weight files (torchvision's AlexNet / VGG16, the `lpips` package's alex.pth / vgg.pth) are read by `LpipsNet.from_files`;
+`LpipsNet.synthetic` builds the same architecture on hash-generated weights, which is what the tests run on.  The implementation is held to the
+published definition, not to the `lpips` package: unpinned against the package.
 """
 from __future__ import annotations
 
@@ -34,12 +35,52 @@ LPIPS_DEFINITION = {
     "min_side": MIN_SIDE,
 }
 
-CHUNK_BYTES = 96 << 20        # activations of one internal chunk of pairs stay below this (one pair at 256 x 256 is 5.9 MB)
+
+def _vgg_layers():
+    out, idx, ci = [], 0, 3
+    for stage, (co, n) in enumerate(((64, 2), (128, 2), (256, 3), (512, 3), (512, 3)), 1):
+        for j in range(1, n + 1):
+            out.append((f"conv{stage}_{j}", f"features.{idx}", co, ci, j == n, j == n and stage < 5))
+            idx, ci = idx + 2, co                     # a ReLU follows every convolution
+        idx += 1                                      # the MaxPool2d(2, 2) that closes the stage (indices 4, 9, 16, 23; the one at 30 is never reached)
+    return tuple(out)
 
 
-def tap_sizes(H: int, W: int) -> List[Tuple[int, int]]:
+# (name, torchvision key, Cout, Cin, tap after its ReLU, 2 x 2 max-pool after the tap): all 3 x 3, stride 1, pad 1
+VGG_LAYERS = _vgg_layers()
+VGG_ARCH_MIN_SIDE = 16                                # four floor-mode halvings leave one pixel at relu5_3
+
+LPIPS_VGG_DEFINITION = {
+    "net": "vgg", "version": "0.1",
+    "input": LPIPS_DEFINITION["input"], "shift": LPIPS_DEFINITION["shift"], "scale": LPIPS_DEFINITION["scale"],
+    "backbone": "torchvision VGG16 features, fp32, 3x3 convolutions with zero padding 1 and stride 1, ReLU after each; taps after relu1_2, relu2_2, relu3_3, relu4_3, "
+                "relu5_3; max-pool 2x2 stride 2 (floor: the last row / column of an odd map is dropped) after taps 1 to 4",
+    "layers": [{"name": n, "key": key, "kernel": 3, "stride": 1, "pad": 1, "channels": [ci, co], "tap": tap} for n, key, co, ci, tap, _ in VGG_LAYERS],
+    "pools": [4, 9, 16, 23],
+    "normalize": LPIPS_DEFINITION["normalize"], "eps": 1e-10, "distance": LPIPS_DEFINITION["distance"],
+    "min_side": MIN_SIDE,                             # the architecture needs 16; the one input stage both networks share refuses below 31 and is kept as it is
+}
+
+DEFINITIONS = {"alex": LPIPS_DEFINITION, "vgg": LPIPS_VGG_DEFINITION}
+NETS = tuple(DEFINITIONS)
+
+CHUNK_BYTES = 96 << 20        # activations of one internal chunk of pairs stay below this (one pair at 256 x 256 is 5.9 MB; on VGG16 134 MB, so one pair per chunk)
+
+
+def _check_net(net: str) -> str:
+    if net not in NETS:
+        raise ValueError(f"LPIPS net {net!r}: expected one of {NETS}")
+    return net
+
+
+def tap_sizes(H: int, W: int, net: str = "alex") -> List[Tuple[int, int]]:
     """spatial size of the five taps of an H x W image"""
     out = []
+    if _check_net(net) == "vgg":
+        for _ in range(5):
+            out.append((H, W))
+            H, W = H // 2, W // 2
+        return out
     for _, _, _, _, k, s, p, pool in LAYERS:
         H, W = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
         out.append((H, W))
@@ -56,51 +97,70 @@ def _check_shapes(what: str, tensors: Dict[str, torch.Tensor], want: Dict[str, T
             raise ValueError(f"{what}: {key!r} has shape {tuple(tensors[key].shape)}, expected {tuple(shape)}")
 
 
-class LpipsNet:
-    """net(recon, original) -> fp64 [B] on the device.  Built from a backbone state dict (torchvision AlexNet keys) and the five 1 x 1 weightings."""
+def _convs(net: str):
+    """(name, torchvision key, Cout, Cin, kernel) of every convolution of a backbone"""
+    if net == "vgg":
+        return [(n, key, co, ci, 3) for n, key, co, ci, _, _ in VGG_LAYERS]
+    return [(n, key, co, ci, k) for n, key, co, ci, k, _, _, _ in LAYERS]
 
-    def __init__(self, backbone: Dict[str, torch.Tensor], linear: Sequence[torch.Tensor], device, source):
+
+def _tap_channels(net: str) -> List[int]:
+    return [co for _, _, co, _, tap, _ in VGG_LAYERS if tap] if net == "vgg" else [co for _, _, co, *_ in LAYERS]
+
+
+class LpipsNet:
+    """net(recon, original) -> fp64 [B] on the device.  Built from a backbone state dict (torchvision AlexNet or VGG16 keys) and the five 1 x 1 weightings."""
+
+    def __init__(self, backbone: Dict[str, torch.Tensor], linear: Sequence[torch.Tensor], device, source, net: str = "alex"):
+        self.net = _check_net(net)
+        self.definition = DEFINITIONS[net]
         self.device = torch.device(device)
         self.source = source
         self.chunk_pairs: Optional[int] = None            # None: sized from CHUNK_BYTES; the tests set it to walk the chunk edges
+        convs, taps = _convs(net), _tap_channels(net)
         _check_shapes("LPIPS backbone", backbone, {f"{key}.{leaf}": ((co, ci, k, k) if leaf == "weight" else (co,))
-                                                   for _, key, co, ci, k, _, _, _ in LAYERS for leaf in ("weight", "bias")})
-        if len(linear) != len(LAYERS):
-            raise ValueError(f"LPIPS linear layers: expected {len(LAYERS)} weightings, got {len(linear)}")
+                                                   for _, key, co, ci, k in convs for leaf in ("weight", "bias")})
+        if len(linear) != len(taps):
+            raise ValueError(f"LPIPS linear layers: expected {len(taps)} weightings, got {len(linear)}")
         self.packed, self.bias, self.lin = [], [], []
-        for (name, key, co, ci, k, _, _, _), w in zip(LAYERS, linear):
-            if w.numel() != co:
-                raise ValueError(f"LPIPS linear layer of {name}: {w.numel()} weights, expected {co}")
+        for name, key, co, ci, k in convs:
             self.packed.append(ops.lpips_pack_conv_weight(backbone[key + ".weight"].detach().float().cpu()).to(self.device))
             self.bias.append(backbone[key + ".bias"].detach().float().contiguous().to(self.device))
+        for i, (co, w) in enumerate(zip(taps, linear)):
+            if w.numel() != co:
+                raise ValueError(f"LPIPS linear layer of tap {i + 1}: {w.numel()} weights, expected {co}")
             self.lin.append(w.detach().float().reshape(co).contiguous().to(self.device))
 
     # ---- construction ----
     @staticmethod
-    def synthetic_tensors():
+    def synthetic_tensors(net: str = "alex"):
         """(backbone state dict, five [1, C, 1, 1] weightings) on the host: hash-generated by tensor name with weights._synth_tensor's recipe; the 1 x 1
         weights are non-negative, as the published ones are"""
         from . import weights as W
         sd = {}
-        for _, key, co, ci, k, _, _, _ in LAYERS:
-            sd[key + ".weight"] = W._synth_tensor(f"lpips.alex.{key}.weight", (co, ci, k, k), "cpu")
-            sd[key + ".bias"] = W._synth_tensor(f"lpips.alex.{key}.bias", (co,), "cpu")
-        lin = [W._synth_tensor(f"lpips.lin{i}.model.1.weight", (1, co, 1, 1), "cpu").abs() for i, (_, _, co, *_) in enumerate(LAYERS)]
+        for _, key, co, ci, k in _convs(_check_net(net)):
+            sd[key + ".weight"] = W._synth_tensor(f"lpips.{net}.{key}.weight", (co, ci, k, k), "cpu")
+            sd[key + ".bias"] = W._synth_tensor(f"lpips.{net}.{key}.bias", (co,), "cpu")
+        prefix = "lpips" if net == "alex" else f"lpips.{net}"
+        lin = [W._synth_tensor(f"{prefix}.lin{i}.model.1.weight", (1, co, 1, 1), "cpu").abs() for i, co in enumerate(_tap_channels(net))]
         return sd, lin
 
     @classmethod
-    def synthetic(cls, device) -> "LpipsNet":
-        sd, lin = cls.synthetic_tensors()
-        return cls(sd, lin, device, "synthetic")
+    def synthetic(cls, device, net: str = "alex") -> "LpipsNet":
+        sd, lin = cls.synthetic_tensors(net)
+        return cls(sd, lin, device, "synthetic", net=net)
 
     @classmethod
-    def from_files(cls, backbone_pth: str, linear_pth: str, device) -> "LpipsNet":
-        """torchvision's AlexNet state dict (keys features.{0,3,6,8,10}.{weight,bias}) and the lpips v0.1 alex.pth (keys lin{0..4}.model.1.weight, [1, C, 1, 1]).
-        A missing key or a wrong shape is an error; other keys are ignored."""
+    def from_files(cls, backbone_pth: str, linear_pth: str, device, net: str = "alex") -> "LpipsNet":
+        """torchvision's AlexNet state dict (keys features.{0,3,6,8,10}.{weight,bias}) and the lpips v0.1 alex.pth (keys lin{0..4}.model.1.weight, [1, C, 1, 1]);
+        with net="vgg" torchvision's vgg16 state dict (features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias}) and the package's vgg.pth (the same
+        lin keys, C = 64, 128, 256, 512, 512).  A missing key or a wrong shape is an error; other keys (the classifier's among them) are ignored."""
+        _check_net(net)
         sd = torch.load(backbone_pth, map_location="cpu", weights_only=True)
         ld = torch.load(linear_pth, map_location="cpu", weights_only=True)
-        _check_shapes(f"LPIPS linear file {linear_pth}", ld, {f"lin{i}.model.1.weight": (1, co, 1, 1) for i, (_, _, co, *_) in enumerate(LAYERS)})
-        return cls(sd, [ld[f"lin{i}.model.1.weight"] for i in range(len(LAYERS))], device, [os.path.basename(backbone_pth), os.path.basename(linear_pth)])
+        taps = _tap_channels(net)
+        _check_shapes(f"LPIPS linear file {linear_pth}", ld, {f"lin{i}.model.1.weight": (1, co, 1, 1) for i, co in enumerate(taps)})
+        return cls(sd, [ld[f"lin{i}.model.1.weight"] for i in range(len(taps))], device, [os.path.basename(backbone_pth), os.path.basename(linear_pth)], net=net)
 
     # ---- the network ----
     def _check(self, recon, original):
@@ -112,9 +172,11 @@ class LpipsNet:
         ops._need_cuda(recon, original)
         return B, H, W
 
-    @staticmethod
-    def _plan(n: int, H: int, W: int):
-        """shapes of the activations of n images, in the order they are produced: input, then per layer the tap and, where there is one, the pooled map"""
+    def _plan(self, n: int, H: int, W: int):
+        """shapes of the activation buffers of n images.  AlexNet: every activation in the order it is produced (input, then per layer the tap and, where there
+        is one, the pooled map).  VGG16: the input, the five taps and the two buffers every other map ping-pongs between (_vgg_steps says who writes where)."""
+        if self.net == "vgg":
+            return [(n,) + s for s in _vgg_steps(H, W)[0]]
         shapes = [(n, H, W, 3)]
         for (_, _, co, _, _, _, _, pool), (h, w) in zip(LAYERS, tap_sizes(H, W)):
             shapes.append((n, h, w, co))
@@ -124,6 +186,8 @@ class LpipsNet:
 
     def _taps(self, recon, original, original_signed, quantize, bufs=None) -> List[torch.Tensor]:
         """the five taps [2B, h, w, C] of one chunk; `bufs`: preallocated activations in _plan's order"""
+        if self.net == "vgg":
+            return self._taps_vgg(recon, original, original_signed, quantize, bufs)
         it = iter(bufs) if bufs is not None else iter(lambda: None, 0)
         x = ops.lpips_input(recon, original, original_signed, quantize, out=next(it))
         taps = []
@@ -133,6 +197,20 @@ class LpipsNet:
             if pool:
                 x = ops.lpips_maxpool3s2(x, out=next(it))
         return taps
+
+    def _taps_vgg(self, recon, original, original_signed, quantize, bufs=None) -> List[torch.Tensor]:
+        n = 2 * recon.shape[0]
+        shapes, steps = _vgg_steps(recon.shape[2], recon.shape[3])
+        if bufs is None:
+            bufs = [torch.empty((n,) + s, dtype=torch.float32, device=recon.device) for s in shapes]
+        held = {0: ops.lpips_input(recon, original, original_signed, quantize, out=bufs[0])}
+        for kind, layer, src, dst, shape in steps:
+            out = bufs[dst].reshape(-1)[:n * shape[0] * shape[1] * shape[2]].view((n,) + shape)      # a ping-pong buffer is viewed at the map's own shape
+            if kind == "conv":
+                held[dst] = ops.lpips_conv2d(held[src], self.packed[layer], self.bias[layer], shape[2], 3, 3, 1, 1, True, out=out)
+            else:
+                held[dst] = ops.lpips_maxpool2s2(held[src], out=out)
+        return [held[1 + i] for i in range(5)]
 
     def features(self, recon: torch.Tensor, original: torch.Tensor, original_signed: bool = True, quantize: bool = False) -> List[torch.Tensor]:
         """the five taps as [2B, C, h, w] fp32 (recon images first, then the originals): what the distance stage is fed, for the tests"""
@@ -148,7 +226,7 @@ class LpipsNet:
         chunk = min(chunk, B)
         shapes = self._plan(2 * chunk, H, W)
         lib = _lib.load()
-        dist_bytes = lib.selftok_lpips_distance_workspace_bytes(chunk, max(h * w for h, w in tap_sizes(H, W)))
+        dist_bytes = lib.selftok_lpips_distance_workspace_bytes(chunk, max(h * w for h, w in tap_sizes(H, W, self.net)))
         if dist_bytes == 0:
             _lib.check(-1, "selftok_lpips_distance_workspace_bytes")
         align = lambda v: -(-v // 256) * 256
@@ -166,3 +244,27 @@ class LpipsNet:
             for i, (t, w) in enumerate(zip(taps, self.lin)):          # taps in index order into out[b0:b1]
                 ops.lpips_distance(t, w, out=out[b0:b1], accumulate=i > 0, workspace=dist_ws)
         return out
+
+
+def _vgg_steps(H: int, W: int):
+    """(per-image buffer shapes, steps) of the VGG16 route.  Buffers: 0 the input, 1 .. 5 the taps, 6 and 7 the ping-pong pair, each as large as the largest
+    map written into it.  A step is (kind, layer index, source buffer, destination buffer, per-image output shape): a convolution that is tapped writes its tap
+    buffer, every other convolution and every pool writes the ping-pong buffer it does not read."""
+    shapes = [(H, W, 3)] + [None] * 5 + [(0, 0, 0), (0, 0, 0)]
+    steps, src, tap, h, w = [], 0, 0, H, W
+    grow = lambda dst, shape: shapes.__setitem__(dst, max(shapes[dst], shape, key=lambda s: s[0] * s[1] * s[2]))
+    for layer, (_, _, co, _, is_tap, pool) in enumerate(VGG_LAYERS):
+        dst = 1 + tap if is_tap else (7 if src == 6 else 6)
+        if is_tap:
+            shapes[dst] = (h, w, co)
+            tap += 1
+        else:
+            grow(dst, (h, w, co))
+        steps.append(("conv", layer, src, dst, (h, w, co)))
+        src = dst
+        if pool:
+            h, w = h // 2, w // 2
+            grow(6, (h, w, co))
+            steps.append(("pool", None, src, 6, (h, w, co)))
+            src = 6
+    return shapes, steps

@@ -1312,6 +1312,55 @@ def image_metrics(recon: torch.Tensor, original: torch.Tensor, original_signed: 
     return out
 
 
+SSIM_PRESETS = ("gaussian", "skimage")
+
+
+def ssim_preset(name: str):
+    """(window, cov_norm) of a named SSIM reading: "gaussian" = evaluate.ssim_window() with population moments (image_metrics' SSIM), "skimage" =
+    skimage.metrics.structural_similarity's defaults, the uniform 7 x 7 window with the sample covariance (cov_norm 49 / 48)"""
+    from .evaluate import ssim_uniform_window, ssim_window
+    if name == "gaussian":
+        return ssim_window(), 1.0
+    if name == "skimage":
+        return ssim_uniform_window(7), 49.0 / 48.0
+    raise ValueError(f"SSIM preset {name!r}: expected one of {SSIM_PRESETS}")
+
+
+def image_ssim(recon: torch.Tensor, original: torch.Tensor, window="skimage", cov_norm: Optional[float] = None, signed_range: bool = True,
+               original_signed: bool = True, quantize: bool = False) -> torch.Tensor:
+    """recon [B, 3, H, W] in [0, 1] against original [B, 3, H, W] (in [-1, 1] when `original_signed`, else in [0, 1]), bf16 or fp32 each -> float64 [B] on the
+    device: the mean SSIM of each image over the valid windows, fp64 (include/selftok_hip_ext.h: selftok_img_ssim).  window: T separable fp64 weights
+    (T odd, 3 .. 11) with `cov_norm` (1.0: population moments; T^2 / (T^2 - 1): sample covariance), or a preset name of SSIM_PRESETS, which sets both.
+    signed_range: operands on [-1, 1] with data range 2 (the reconstruction becomes 2 r - 1), else on [0, 1] with data range 1.  `quantize`: on the bytes
+    `image_to_u8` would write for both.  No host synchronisation; H, W >= T."""
+    if isinstance(window, str):
+        if cov_norm is not None:
+            raise ValueError(f"image_ssim: the preset {window!r} sets cov_norm itself")
+        window, cov_norm = ssim_preset(window)
+    elif cov_norm is None:
+        raise ValueError("image_ssim: a window given as weights needs cov_norm (1.0: population moments)")
+    _need_cuda(recon, original)
+    for name, t in (("recon", recon), ("original", original)):
+        if t.dtype not in (torch.bfloat16, torch.float32):
+            raise _lib.SelftokHipError(f"image_ssim: `{name}` dtype {t.dtype}: expected bfloat16 or float32")
+    if recon.dim() != 4 or recon.shape[1] != 3 or tuple(original.shape) != tuple(recon.shape):
+        raise _lib.SelftokHipError(f"image_ssim: expected two [B, 3, H, W] tensors of one shape, got {tuple(recon.shape)} and {tuple(original.shape)}")
+    import numpy as np
+    win = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+    recon, original = recon.contiguous(), original.contiguous()
+    B, _, H, W = recon.shape
+    lib = _lib.load()
+    nbytes = lib.selftok_img_ssim_workspace_bytes(B, H, W, int(win.size))
+    if nbytes == 0:
+        _lib.check(-1, "selftok_img_ssim_workspace_bytes")
+    ws = _img_metrics_ws(recon.device, nbytes)
+    out = torch.empty(B, dtype=torch.float64, device=recon.device)
+    _lib.check(lib.selftok_img_ssim(_p(recon), int(recon.dtype == torch.bfloat16), _p(original), int(original.dtype == torch.bfloat16), int(bool(original_signed)),
+                                    int(bool(quantize)), win.ctypes.data, int(win.size), float(cov_norm), int(bool(signed_range)), _p(out), _p(ws), ws.numel(), B, H, W,
+                                    _stream()), "selftok_img_ssim")
+    return out
+
+
 # ---- LPIPS stages (csrc/lpips.hip, include/selftok_hip_ext.h): channels-last fp32 activations [N, H, W, C] ----
 def _lpips_f32(name: str, t: torch.Tensor, dim: int) -> torch.Tensor:
     if t.dtype != torch.float32 or t.dim() != dim:
@@ -1367,6 +1416,20 @@ def lpips_maxpool3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> tor
     elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
         raise _lib.SelftokHipError(f"lpips_maxpool3s2: `out` must be a contiguous float32 {shape}, got {out.dtype} {tuple(out.shape)}")
     _lib.check(_lib.load().selftok_lpips_maxpool3s2_f32(_p(x), _p(out), N, H, W, C, _stream()), "selftok_lpips_maxpool3s2_f32")
+    return out
+
+
+def lpips_maxpool2s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [N, H, W, C] fp32 channels-last -> [N, H // 2, W // 2, C]: 2 x 2 windows, stride 2, floor mode, no padding (VGG16's MaxPool2d(2, 2))"""
+    _need_cuda(x, out)
+    x = _lpips_f32("x", x, 4)
+    N, H, W, C = x.shape
+    shape = (N, H // 2, W // 2, C)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"lpips_maxpool2s2: `out` must be a contiguous float32 {shape}, got {out.dtype} {tuple(out.shape)}")
+    _lib.check(_lib.load().selftok_lpips_maxpool2s2_f32(_p(x), _p(out), N, H, W, C, _stream()), "selftok_lpips_maxpool2s2_f32")
     return out
 
 

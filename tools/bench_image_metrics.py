@@ -10,7 +10,13 @@
 Same process for every variant, 3 warm-up runs + `--reps` repetitions (the emulation: 1 + 3), median and min..max.  Nothing is asserted about
 speed; the device values are checked against the emulation before anything is timed.  Prints a text report and one JSON line.
 
-    python tools/bench_image_metrics.py [--reps 15] [--no-pipeline] [--out profiles/image_metrics.txt]"""
+    python tools/bench_image_metrics.py [--reps 15] [--no-pipeline] [--out profiles/image_metrics.txt]
+
+--variant skimage: the same protocol for `ops.image_ssim` (csrc/image_ssim.hip) -- the "skimage" preset (uniform 7 x 7, sample covariance) on both ranges
+and on the bytes, the uniform and the Gaussian 11-tap window -- next to `ops.image_metrics` on the same buffers, A / B alternating inside one loop; the values
+are checked against the emulation of tests/ssim_variant_cases.py first, and the Gaussian reading against column 0 of image_metrics bit for bit.  One JSON object.
+
+    python tools/bench_image_metrics.py --variant skimage [--reps 15] [--batches 64] [--out profiles/ssim_variants.json]"""
 import argparse, json, os, sys, time
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,6 +32,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=15)
 ap.add_argument("--batches", default="64,256")
 ap.add_argument("--no-pipeline", action="store_true")
+ap.add_argument("--variant", default="gaussian", choices=["gaussian", "skimage"], help="skimage: time ops.image_ssim's readings next to ops.image_metrics instead")
 ap.add_argument("--out", default=None, help="also write the report to this file")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -72,6 +79,56 @@ def emulation(recon, orig):
     res = list(pool.map(lambda p: M.metrics(recon[p], orig[p], True, True, False), parts))
     return np.concatenate([r[0] for r in res]), np.concatenate([r[1] for r in res])
 
+
+def ssim_variants():
+    import ssim_variant_cases as SV
+    res = {"tool": "bench_image_metrics --variant skimage", "size": S, "reps": a.reps, "device": torch.cuda.get_device_name(0),
+           "protocol": "one process, warm, 3 warm-up runs + reps repetitions, HIP events around one call, A / B alternating; median [min..max]"}
+    for B in [int(b) for b in a.batches.split(",")]:
+        orig = synth.synthetic_images(B, size=S).to(dev)
+        recon = ((orig + 1) / 2 + 0.1 * (synth.synthetic_images(B, size=S, first_index=B).to(dev))).clamp_(0, 1).to(torch.bfloat16)
+        recon_h, orig_h = recon.float().cpu().numpy(), orig.cpu().numpy()
+        calls = {"image_metrics_ssim_and_mse": lambda: ops.image_metrics(recon, orig),
+                 "ssim_t7_uniform_sample_signed": lambda: ops.image_ssim(recon, orig, "skimage", None, True),
+                 "ssim_t7_uniform_sample_unsigned": lambda: ops.image_ssim(recon, orig, "skimage", None, False),
+                 "ssim_t7_uniform_sample_signed_u8": lambda: ops.image_ssim(recon, orig, "skimage", None, True, True, True),
+                 "ssim_t11_uniform_sample_signed": lambda: ops.image_ssim(recon, orig, SV.uniform_window(11), SV.sample_cov_norm(11), True),
+                 "ssim_t11_gaussian_population_unsigned": lambda: ops.image_ssim(recon, orig, "gaussian", None, False)}
+        n = min(B, 8)                                                                           # the emulation of the first images, one thread
+        want = {"ssim_t7_uniform_sample_signed": SV.ssim(recon_h[:n], orig_h[:n], SV.uniform_window(7), SV.sample_cov_norm(7), True, True, True, False),
+                "ssim_t7_uniform_sample_unsigned": SV.ssim(recon_h[:n], orig_h[:n], SV.uniform_window(7), SV.sample_cov_norm(7), False, True, True, False),
+                "ssim_t7_uniform_sample_signed_u8": SV.ssim(recon_h[:n], orig_h[:n], SV.uniform_window(7), SV.sample_cov_norm(7), True, True, True, True),
+                "ssim_t11_uniform_sample_signed": SV.ssim(recon_h[:n], orig_h[:n], SV.uniform_window(11), SV.sample_cov_norm(11), True, True, True, False)}
+        r = {"checked_images": n}
+        for k, w in want.items():
+            got = calls[k]().cpu().numpy()
+            r[k] = {"mean": float(got.mean()), "max_abs_d_vs_emulation": float(np.abs(got[:n] - w).max())}
+            assert r[k]["max_abs_d_vs_emulation"] <= 1e-10, (k, r[k])
+        old, new = calls["image_metrics_ssim_and_mse"]().cpu().numpy()[:, 0], calls["ssim_t11_gaussian_population_unsigned"]().cpu().numpy()
+        r["ssim_t11_gaussian_population_unsigned"] = {"mean": float(new.mean()), "bit_equal_to_image_metrics_column_0": bool(np.array_equal(old.view(np.uint64), new.view(np.uint64)))}
+        assert r["ssim_t11_gaussian_population_unsigned"]["bit_equal_to_image_metrics_column_0"]
+        r["image_metrics_ssim_and_mse"] = {"mean": float(old.mean())}
+        times = {k: [] for k in calls}
+        for fn in calls.values():
+            for _ in range(3):
+                fn()
+        for _ in range(a.reps):                                                                 # alternating
+            for k, fn in calls.items():
+                times[k] += event_timed(fn, 1, warm=0)
+        for k in calls:
+            r[k]["events"] = stats(times[k])
+        r["gpixel_per_s_t7"] = round(B * 3 * S * S / (r["ssim_t7_uniform_sample_signed"]["events"]["median_ms"] * 1e-3) / 1e9, 2)
+        res[f"B{B}"] = r
+    print(json.dumps(res, indent=1), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(json.dumps(res, indent=1) + "\n")
+
+
+if a.variant == "skimage":
+    ssim_variants()
+    pool.shutdown()
+    sys.exit(0)
 
 res = {"tool": "bench_image_metrics", "size": S, "reps": a.reps, "device": torch.cuda.get_device_name(0), "emulation_threads": THREADS}
 for B in [int(b) for b in a.batches.split(",")]:

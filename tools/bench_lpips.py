@@ -9,7 +9,14 @@
 3 warm-up runs + `--reps` repetitions, median and min..max.  Nothing is asserted about speed; the device values are checked against the fp64
 emulation (tests/lpips_cases.py, on the first `--check` pairs) before anything is timed.  Writes one JSON object.
 
-    python tools/bench_lpips.py [--reps 15] [--batch 64] [--no-pipeline] [--out profiles/lpips.json]"""
+    python tools/bench_lpips.py [--reps 15] [--batch 64] [--no-pipeline] [--out profiles/lpips.json]
+
+--net vgg: the same protocol for LPIPS on the VGG16 backbone (synthetic weights) -- `LpipsNet(net="vgg").__call__` and the AlexNet network's call A / B
+alternating inside one loop on the same pairs, then every kernel of the VGG route on the shapes of one internal chunk: the 13 convolutions' share of the
+call and their fraction of the fp32 matrix peak (157.3 TFLOP/s, v_mfma_f32_32x32x2_f32).  Values are checked against the fp64 emulation of
+tests/lpips_vgg_cases.py (on the first `--check` pairs) first.
+
+    python tools/bench_lpips.py --net vgg [--reps 15] [--batch 64] [--check 1] [--out profiles/lpips_vgg.json]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,6 +35,7 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--check", type=int, default=4, help="pairs checked against the fp64 emulation before timing")
 ap.add_argument("--no-pipeline", action="store_true")
 ap.add_argument("--out", default=None)
+ap.add_argument("--net", default="alex", choices=["alex", "vgg"])
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(dev)
@@ -53,6 +61,71 @@ def event_timed(fn, reps, warm=3):
         fn()
     return [event_time(fn) for _ in range(reps)]
 
+
+def bench_vgg():
+    import lpips_vgg_cases as V
+    from selftoktokenizer_amd import lpips as LP
+    PEAK = 157.3                                                                                # TFLOP/s, fp32 matrix (MFMA f32 in / f32 accumulate)
+    vgg, alex = LpipsNet.synthetic(dev, net="vgg"), LpipsNet.synthetic(dev)
+    orig = synth.synthetic_images(B, size=S).to(dev)
+    recon = ((synth.synthetic_images(B, size=S, first_index=B).to(dev) + 1) / 2).clamp_(0, 1).to(torch.bfloat16)
+    n = min(a.check, B)
+    got, got_alex = vgg(recon, orig).cpu().numpy(), alex(recon, orig).cpu().numpy()
+    want = V.emulate(recon[:n].float().cpu().numpy(), orig[:n].cpu().numpy(), True, True, False)
+    gate = 4.0 * V.fp32_relative_error()
+    res = {"tool": "bench_lpips --net vgg", "size": S, "pairs": B, "reps": a.reps, "device": torch.cuda.get_device_name(0), "weights": vgg.source,
+           "protocol": "one process, warm, 3 warm-up runs + reps repetitions, HIP events around one call, A / B alternating; median [min..max]",
+           "lpips_vgg_mean": float(got.mean()), "lpips_alex_mean": float(got_alex.mean()), "checked_pairs": n,
+           "max_rel_error_vs_fp64_emulation": float((np.abs(got[:n] - want) / want).max()), "gate": gate}
+    assert res["max_rel_error_vs_fp64_emulation"] <= gate and want.min() >= 0.05, res
+    tv, ta = [], []
+    for _ in range(3):
+        vgg(recon, orig); alex(recon, orig)
+    for _ in range(a.reps):
+        tv.append(event_time(lambda: vgg(recon, orig)))
+        ta.append(event_time(lambda: alex(recon, orig)))
+    res["vgg_call_events"], res["alex_call_events"] = stats(tv), stats(ta)
+    per_pair = 2 * 4 * sum(h * w * c for _, h, w, c in vgg._plan(1, S, S))
+    chunk = min(B, vgg.chunk_pairs or max(1, LP.CHUNK_BYTES // per_pair))
+    chunks = -(-B // chunk)
+    res["activation_bytes_per_pair"], res["chunk_pairs"], res["chunks_per_call"] = per_pair, chunk, chunks
+    kern, conv_ms, conv_flop, tap = {}, 0.0, 0.0, 0
+    x = ops.lpips_input(recon[:chunk], orig[:chunk])
+    kern["input"] = stats(event_timed(lambda: ops.lpips_input(recon[:chunk], orig[:chunk]), a.reps))
+    for (name, _, co, ci, is_tap, pool), packed, bias in zip(LP.VGG_LAYERS, vgg.packed, vgg.bias):
+        xin = x
+        t = stats(event_timed(lambda: ops.lpips_conv2d(xin, packed, bias, co, 3, 3, 1, 1, True), a.reps))
+        flop = 2.0 * xin.shape[0] * xin.shape[1] * xin.shape[2] * co * ci * 9
+        t["tflops"] = round(flop / (t["median_ms"] * 1e-3) / 1e12, 2)
+        t["fraction_of_fp32_matrix_peak"] = round(t["tflops"] / PEAK, 4)
+        kern[name] = t
+        conv_ms, conv_flop = conv_ms + t["median_ms"], conv_flop + flop
+        x = ops.lpips_conv2d(xin, packed, bias, co, 3, 3, 1, 1, True)
+        if is_tap:
+            cur, lw = x, vgg.lin[tap]
+            kern["distance_" + name] = stats(event_timed(lambda: ops.lpips_distance(cur, lw), a.reps))
+            tap += 1
+        if pool:
+            cur = x
+            kern["pool_" + name] = stats(event_timed(lambda: ops.lpips_maxpool2s2(cur), a.reps))
+            x = ops.lpips_maxpool2s2(cur)
+    res["per_kernel_one_chunk"] = kern
+    call = res["vgg_call_events"]["median_ms"]
+    res["convolutions_ms_per_call"] = round(conv_ms * chunks, 3)
+    res["convolutions_share_of_call"] = round(conv_ms * chunks / call, 4)
+    res["convolutions_tflops"] = round(conv_flop * chunks / (conv_ms * chunks * 1e-3) / 1e12, 2)
+    res["convolutions_fraction_of_fp32_matrix_peak"] = round(res["convolutions_tflops"] / PEAK, 4)
+    res["call_tflops_convolution_flop_over_call_time"] = round(conv_flop * chunks / (call * 1e-3) / 1e12, 2)
+    res["vgg_over_alex_call_time"] = round(call / res["alex_call_events"]["median_ms"], 2)
+    print(json.dumps(res, indent=1), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(json.dumps(res, indent=1) + "\n")
+
+
+if a.net == "vgg":
+    bench_vgg()
+    sys.exit(0)
 
 net = LpipsNet.synthetic(dev)
 orig = synth.synthetic_images(B, size=S).to(dev)                                                # fp32 in [-1, 1)

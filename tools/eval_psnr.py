@@ -10,7 +10,12 @@ with --ssim also `ssim_mean` / `ssim_each` (the SSIM column of the reference's r
 with --lpips-backbone FILE --lpips-linear FILE (torchvision's AlexNet state dict and the lpips package's v0.1 alex.pth) also `lpips_mean` / `lpips_each`
 (selftoktokenizer_amd/lpips.py).  `--lpips` alone is accepted with --synthetic only: the hash-generated LPIPS network, labelled "synthetic" in the line;
 with --fid-weights FILE (pytorch-fid's pt_inception-2015-12-05 state dict) also `rfid` per decoder (selftoktokenizer_amd/fid.py: InceptionV3 pool3 features
-and the fp64 statistics on the GPU, the Frechet distance on the host); `--fid` alone, like `--lpips`, with --synthetic only."""
+and the fp64 statistics on the GPU, the Frechet distance on the host); `--fid` alone, like `--lpips`, with --synthetic only;
+with --ssim-skimage [--ssim-range signed|unsigned] also `ssim_skimage_mean` / `ssim_skimage_each`: skimage.metrics.structural_similarity's defaults (uniform
+7 x 7 window, sample covariance) in fp64, on [-1, 1] data with data_range 2 (signed, the default) or on [0, 1] data;
+with --lpips-vgg BACKBONE.pth LINEAR.pth (torchvision's vgg16 state dict and the lpips package's v0.1 vgg.pth) also LPIPS on the VGG16 backbone; given
+together with the AlexNet network the two are reported as `lpips_alex_*` and `lpips_vgg_*`.  `--lpips-vgg` without files: with --synthetic only.
+One run with --ssim --ssim-skimage --lpips... --lpips-vgg... --fid... prints PSNR, both SSIM readings, both LPIPS readings and rFID."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -39,10 +44,15 @@ ap.add_argument("--metrics-u8", action="store_true", help="with --ssim: take PSN
 ap.add_argument("--lpips-backbone", default=None, help="torchvision AlexNet state dict (features.{0,3,6,8,10}.{weight,bias}); with --lpips-linear: also LPIPS (alex, v0.1) of every image, on the GPU")
 ap.add_argument("--lpips-linear", default=None, help="the lpips package's v0.1 alex.pth (lin{0..4}.model.1.weight)")
 ap.add_argument("--lpips", action="store_true", help="with --synthetic and no weight files: LPIPS on the hash-generated network (values of the published definition on synthetic weights)")
+ap.add_argument("--ssim-skimage", action="store_true", help="also skimage.metrics.structural_similarity's default SSIM (uniform 7 x 7 window, sample covariance, fp64) of every image, on the GPU")
+ap.add_argument("--ssim-range", default="signed", choices=["signed", "unsigned"], help="with --ssim-skimage: on [-1, 1] data with data_range 2 (signed) or on [0, 1] data with data_range 1")
+ap.add_argument("--lpips-vgg", nargs="*", default=None, metavar="PTH", help="BACKBONE.pth LINEAR.pth: torchvision's vgg16 state dict and the lpips package's v0.1 vgg.pth: also LPIPS on the VGG16 backbone; no files: the hash-generated network, with --synthetic only")
 ap.add_argument("--fid-weights", default=None, help="pytorch-fid's pt_inception-2015-12-05 state dict: also rFID (InceptionV3 pool3) of every decoder's reconstructions against the originals")
 ap.add_argument("--fid", action="store_true", help="with --synthetic and no weight file: rFID on the hash-generated InceptionV3 (the published definition on synthetic weights)")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file (rank 0)")
 a = ap.parse_args()
+if a.lpips_vgg is not None and (len(a.lpips_vgg) not in (0, 2) or (not a.lpips_vgg and not a.synthetic)):
+    ap.error("--lpips-vgg takes BACKBONE.pth LINEAR.pth, or nothing together with --synthetic (the published VGG16 and LPIPS weights are not shipped)")
 if a.synthetic and a.preprocess != "reference":
     ap.error("--preprocess applies to image files: --synthetic images are generated at data_size")
 
@@ -81,17 +91,26 @@ lpips_net = None
 if a.lpips_backbone or a.lpips:
     from selftoktokenizer_amd.lpips import LpipsNet
     lpips_net = LpipsNet.from_files(a.lpips_backbone, a.lpips_linear, dev) if a.lpips_backbone else LpipsNet.synthetic(dev)
+vgg_net = None
+if a.lpips_vgg is not None:
+    from selftoktokenizer_amd.lpips import LpipsNet
+    vgg_net = LpipsNet.from_files(a.lpips_vgg[0], a.lpips_vgg[1], dev, net="vgg") if a.lpips_vgg else LpipsNet.synthetic(dev, net="vgg")
 if a.fid and not a.fid_weights and not a.synthetic:
     ap.error("--fid without --fid-weights needs --synthetic: the published InceptionV3 weights are not shipped")
 fid_net = None
 if a.fid_weights or a.fid:
     from selftoktokenizer_amd.fid import InceptionNet
     fid_net = InceptionNet.from_files(a.fid_weights, dev) if a.fid_weights else InceptionNet.synthetic(dev)
-if a.metrics_u8 and not (a.ssim or lpips_net or fid_net):
-    ap.error("--metrics-u8 needs --ssim, LPIPS or rFID (the device metrics route)")
+if a.metrics_u8 and not (a.ssim or a.ssim_skimage or lpips_net or vgg_net or fid_net):
+    ap.error("--metrics-u8 needs --ssim, --ssim-skimage, LPIPS or rFID (the device metrics route)")
 mkw = dict(metrics=("psnr", "ssim"), metrics_u8=a.metrics_u8) if a.ssim else {}
 if lpips_net is not None:
     mkw = dict(metrics=("psnr", "ssim", "lpips") if a.ssim else ("psnr", "lpips"), metrics_u8=a.metrics_u8, lpips=lpips_net)
+if vgg_net is not None:                          # a sequence of networks: keys by backbone, `lpips_vgg_*` and, with the AlexNet network, `lpips_alex_*`
+    mkw = dict(mkw, metrics=tuple(m for m in mkw.get("metrics", ("psnr",)) if m != "lpips") + ("lpips",), metrics_u8=a.metrics_u8,
+               lpips=[lpips_net, vgg_net] if lpips_net is not None else [vgg_net])
+if a.ssim_skimage:
+    mkw = dict(mkw, metrics=tuple(mkw.get("metrics", ("psnr",))) + ("ssim_skimage",), metrics_u8=a.metrics_u8, ssim_skimage_signed=a.ssim_range == "signed")
 if fid_net is not None:
     mkw = dict(mkw, metrics=tuple(mkw.get("metrics", ("psnr",))) + ("rfid",), metrics_u8=a.metrics_u8, fid=fid_net)
 res = E.evaluate(pipe, load, n, batch=a.batch, decoders=decoders, noise_fn=noise, seed=a.seed, renderer_pipe=rpipe, verbose=True, **mkw)
@@ -107,6 +126,11 @@ if rank == 0:
     if lpips_net is not None:                    # BASELINE.md rows 17-18; neither the decoder nor the LPIPS variant is stated (alex v0.1 is the package default)
         line["lpips_weights"] = lpips_net.source
         line["paper_reference_lpips"] = {"512": 0.084, "1024": 0.063, "note": "assets/results_table.PNG: needs the published tokenizer, AlexNet and LPIPS weights"}
+    if vgg_net is not None:
+        line["lpips_vgg_weights"] = vgg_net.source
+        line.setdefault("paper_reference_lpips", {"512": 0.084, "1024": 0.063, "note": "assets/results_table.PNG: the LPIPS network is not stated; needs the published tokenizer, backbone and LPIPS weights"})
+    if a.ssim_skimage:
+        line.setdefault("paper_reference_ssim", {"512": 0.709, "1024": 0.805, "note": "assets/results_table.PNG: ImageNet-val 50k at 256 x 256, decoder and SSIM variant not stated; needs the published weights"})
     if fid_net is not None:                      # the variant the paper used is not stated; rFID depends on N below 2049 images (rfid_rank_deficient)
         line["fid_weights"] = fid_net.source
         line["paper_reference_rfid"] = {"note": "assets/results_table.PNG: ImageNet-val 50k at 256 x 256; needs the published tokenizer and InceptionV3 weights"}
