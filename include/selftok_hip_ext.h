@@ -348,6 +348,32 @@ int selftok_manifold_count_nn_f32(const float* x, const float* a, const float* r
 size_t selftok_kid_sums_f32_workspace_bytes(int S, int m, int D);
 int selftok_kid_sums_f32(const float* xs, const float* ys, double* sums, void* workspace, size_t workspace_bytes, int S, int m, int D, hipStream_t stream);
 
+/* ---- decode stream: one sampler step per slot (csrc/decode_stream.hip) --------------------------------------------------------------
+ * A batch of B slots in which slot b is at its own sampler step step[b] (int32, device).  A slot is ACTIVE iff 0 <= step[b] < n_steps.
+ * Both entries are stateless, capturable, without workspace, atomics or scratch; every refusal is decided on the host (SELFTOK_EINVAL with
+ * a message, nothing launched).
+ *
+ * stream_prepare: limit [n_steps] int32 = min(k + 1, K) of every step; coef [n_steps, 4] = (dt, t, t_prev, 0); pattern_words [B, W],
+ *   W = ceil(K / 32), the slot's visibility pattern in the bit layout of the attention's kmask (null: every key); mod_table [n_steps, R]
+ *   and optionally mod_table_uncond [n_steps, R] (it and mods_uncond_out are null together); segs_host: n_segs <= 32 pairs (first column,
+ *   width) on the HOST, ascending, widths multiples of 4 that tile the R columns exactly.  Writes
+ *     kwords_out [B, W] = pattern_words[b] & bits(j < limit[step[b]]), bits at j >= K zero;
+ *     coef_out [B, 4]   = (dt, t, t_prev, 1.0) of the slot's step;
+ *     mods_out [B * R]  = row step[b] of the table, SEGMENT-MAJOR: segment s is the contiguous [B, width_s] slab at float offset B * first_s.
+ *   An idle slot gets zero words, a zero coefficient row and the table's row 0.  1 <= K <= 2048, B <= 65535, 4 <= R <= 2^28.
+ *
+ * unpatchify_cfg_euler_rows: selftok_unpatchify_cfg_euler_f32 with dt = coef_rows[b][0] for every slot whose coef_rows[b][3] != 0 -- the
+ *   same bits as that entry gives for the sample alone -- and step_out[b] = step[b] + 1; x0_param != 0: x_out = v + t_prev * (x - v) / t
+ *   instead (v the CFG mix; fp32, uncontracted: difference, product, product with the fp32 reciprocal of t, sum).  A slot whose
+ *   coef_rows[b][3] == 0 gets x_out[b] = x[b] byte for byte and step_out[b] = step[b]; nothing of y is read for it.  x_out == x and
+ *   step_out == step are allowed.  y_uncond null: no CFG mix. */
+int selftok_stream_prepare(const int* step, const int* limit, const float* coef, const unsigned* pattern_words, const float* mod_table,
+                           const float* mod_table_uncond, const int* segs_host, int n_segs, unsigned* kwords_out, float* coef_out,
+                           float* mods_out, float* mods_uncond_out, int B, int K, int n_steps, long R, hipStream_t stream);
+int selftok_unpatchify_cfg_euler_rows_f32(const float* y_cond, const float* y_uncond, const float* x, float* x_out, const float* coef_rows,
+                                          const int* step, int* step_out, int B, int C, int hp, int wp, float cfg_scale, int x0_param,
+                                          hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,8 @@ EXT_SIGNATURES = {
     "selftok_manifold_count_nn_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "selftok_kid_sums_f32_workspace_bytes": (_sz, [_i, _i, _i]),
     "selftok_kid_sums_f32": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "selftok_stream_prepare": (_i, [_vp] * 7 + [_i] + [_vp] * 4 + [_i, _i, _i, _l, _vp]),
+    "selftok_unpatchify_cfg_euler_rows_f32": (_i, [_vp] * 7 + [_i, _i, _i, _i, _f, _i, _vp]),
 }
 
 

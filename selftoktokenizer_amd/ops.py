@@ -1733,3 +1733,65 @@ def kid_sums(xs: torch.Tensor, ys: torch.Tensor, S: int, m: int, *, out: Optiona
         raise _lib.SelftokHipError(f"kid_sums: `out` must be a contiguous float64 [{S}, 3], got {out.dtype} {tuple(out.shape)}")
     _lib.check(lib.selftok_kid_sums_f32(_p(xs), _p(ys), _p(out), _p(ws), ws.numel() * ws.element_size(), S, m, D, _stream()), "selftok_kid_sums_f32")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# decode stream: one sampler step per slot (csrc/decode_stream.hip)
+# ----------------------------------------------------------------------------------------------
+
+def _stream_check(what: str, t, dtype, shape):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise _lib.SelftokHipError(f"{what}: expected a contiguous {dtype} {list(shape)}, got {t.dtype} {list(t.shape)}")
+
+
+def stream_prepare(step, limit, coef, pattern_words, table, table_uncond, segs, kwords_out, coef_out, mods_out, mods_uncond_out=None, *, K: int):
+    """step int32 [B] (a slot is active iff 0 <= step < n_steps), limit int32 [n_steps], coef fp32 [n_steps, 4] = (dt, t, t_prev, 0),
+    pattern_words int32 [B, ceil(K / 32)] or None (every key), table / table_uncond fp32 [n_steps, R] (the second or None), segs: a HOST
+    numpy int32 [S, 2] of (first column, width) -> writes kwords_out [B, W] (the slot's pattern below its step's limit), coef_out [B, 4] =
+    (dt, t, t_prev, active) and the slots' table rows into mods_out / mods_uncond_out [B * R], segment-major: segment s is the
+    contiguous [B, width_s] tensor at offset B * first_s.  No host synchronisation, nothing allocated."""
+    import numpy as np
+    _need_cuda(step, limit, coef, pattern_words, table, table_uncond, kwords_out, coef_out, mods_out, mods_uncond_out)
+    if not isinstance(segs, np.ndarray) or segs.dtype != np.int32 or segs.ndim != 2 or segs.shape[1] != 2 or not segs.flags.c_contiguous:
+        raise _lib.SelftokHipError("stream_prepare: `segs` must be a C-contiguous host numpy int32 [S, 2]")
+    B, W = step.shape[0], (int(K) + 31) // 32
+    n_steps, R = table.shape
+    _stream_check("stream_prepare: step", step, torch.int32, (B,))
+    _stream_check("stream_prepare: limit", limit, torch.int32, (n_steps,))
+    _stream_check("stream_prepare: coef", coef, torch.float32, (n_steps, 4))
+    _stream_check("stream_prepare: table", table, torch.float32, (n_steps, R))
+    _stream_check("stream_prepare: kwords_out", kwords_out, torch.int32, (B, W))
+    _stream_check("stream_prepare: coef_out", coef_out, torch.float32, (B, 4))
+    _stream_check("stream_prepare: mods_out", mods_out, torch.float32, (B * R,))
+    if pattern_words is not None:
+        _stream_check("stream_prepare: pattern_words", pattern_words, torch.int32, (B, W))
+    if (table_uncond is None) != (mods_uncond_out is None):
+        raise _lib.SelftokHipError("stream_prepare: table_uncond and mods_uncond_out come together")
+    if table_uncond is not None:
+        _stream_check("stream_prepare: table_uncond", table_uncond, torch.float32, (n_steps, R))
+        _stream_check("stream_prepare: mods_uncond_out", mods_uncond_out, torch.float32, (B * R,))
+    _lib.check(_lib.load().selftok_stream_prepare(_p(step), _p(limit), _p(coef), _p(pattern_words), _p(table), _p(table_uncond), segs.ctypes.data, segs.shape[0],
+                                                  _p(kwords_out), _p(coef_out), _p(mods_out), _p(mods_uncond_out), B, int(K), n_steps, R, _stream()),
+               "selftok_stream_prepare")
+
+
+def unpatchify_cfg_euler_rows(y_cond, y_uncond, x, coef_rows, step, *, cfg_scale: float = 1.0, x0_param: bool = False, x_out=None, step_out=None):
+    """`unpatchify_cfg_euler` with one dt per slot: coef_rows fp32 [B, 4] = (dt, t, t_prev, active) as `stream_prepare` writes it, step int32 [B].
+    An active slot gets the Euler update (x0_param: v + t_prev * (x - v) / t) and step + 1, an idle one keeps x and step byte for byte.
+    x_out / step_out None: IN PLACE.  -> (x_out, step_out)"""
+    _need_cuda(y_cond, y_uncond, x, coef_rows, step, x_out, step_out)
+    B, C, Hh, Ww = x.shape
+    hp, wp = Hh // 2, Ww // 2
+    x_out = x if x_out is None else x_out
+    step_out = step if step_out is None else step_out
+    _stream_check("unpatchify_cfg_euler_rows: x", x, torch.float32, (B, C, 2 * hp, 2 * wp))
+    _stream_check("unpatchify_cfg_euler_rows: x_out", x_out, torch.float32, (B, C, 2 * hp, 2 * wp))
+    _stream_check("unpatchify_cfg_euler_rows: y_cond", y_cond, torch.float32, (B, hp * wp, 4 * C))
+    if y_uncond is not None:
+        _stream_check("unpatchify_cfg_euler_rows: y_uncond", y_uncond, torch.float32, (B, hp * wp, 4 * C))
+    _stream_check("unpatchify_cfg_euler_rows: coef_rows", coef_rows, torch.float32, (B, 4))
+    _stream_check("unpatchify_cfg_euler_rows: step", step, torch.int32, (B,))
+    _stream_check("unpatchify_cfg_euler_rows: step_out", step_out, torch.int32, (B,))
+    _lib.check(_lib.load().selftok_unpatchify_cfg_euler_rows_f32(_p(y_cond), _p(y_uncond), _p(x), _p(x_out), _p(coef_rows), _p(step), _p(step_out), B, C, hp, wp,
+                                                                 float(cfg_scale), int(bool(x0_param)), _stream()), "selftok_unpatchify_cfg_euler_rows_f32")
+    return x_out, step_out

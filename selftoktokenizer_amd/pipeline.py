@@ -19,7 +19,7 @@ from . import _lib, gemm_tune, ops, weights as W
 from .encoder import QformerEncoderGPU, sinusoid_host
 from .mmdit import MMDiTGPU
 from .modsurface import ModuleSurface
-from .schedule import DiTiCont, FlowSchedule, context_plan, pattern_groups, request_pattern
+from .schedule import DiTiCont, FlowSchedule, SlotSchedule, StreamFull, context_plan, pattern_groups, request_pattern
 from .vae import AutoencoderKLGPU
 
 SD3_SCALE, SD3_SHIFT = 1.5305, 0.0609     # SD3LatentFormat (sd3/sd3_impls.py:136-138)
@@ -516,6 +516,28 @@ class SelftokPipeline():
         self._say('End decoding.')
         return (recons, pred_x0) if return_latent else recons
 
+    def decode_stream(self, slots: int, uncond_scale: float = 1.0, max_steps: Optional[int] = None, context: str = "live",
+                      return_latent: bool = False) -> "DecodeStream":
+        """(extension) in-flight batching of the sampler: a `DecodeStream` of `slots` slots in which every request is at its OWN sampler step --
+        `submit` a request whenever a slot is free, `step()` advances all of them by one step and returns the ones that finished.  See DecodeStream."""
+        return DecodeStream(self, slots, uncond_scale, max_steps, context, return_latent)
+
+    def decoding_stream(self, requests, slots: int = 8, **stream_kw):
+        """(extension) `decoding` over an iterable of (ids [K], kwargs of DecodeStream.submit) through one decode stream that is kept full:
+        yields (index of the request, image [3, H, W]) in completion order."""
+        stream = self.decode_stream(slots, **stream_kw)
+        index, it, pending = {}, iter(enumerate(requests)), True
+        while pending or stream.in_flight:
+            while pending and stream.free_slots:
+                nxt = next(it, None)
+                if nxt is None:
+                    pending = False
+                    break
+                i, (ids, kw) = nxt
+                index[stream.submit(ids, **(kw or {}))] = i
+            for done in stream.step() if stream.in_flight else ():
+                yield (index.pop(done[0]),) + tuple(done[1:])
+
     @_on_own_device
     @torch.no_grad()
     def decoding_with_renderer(self, idx, device=None, return_latent: bool = False):
@@ -528,3 +550,188 @@ class SelftokPipeline():
         recons = self._to_pixels(pred_x0)
         self._say('End decoding with Renderer.')
         return (recons, pred_x0) if return_latent else recons
+
+
+class DecodeStream:
+    """In-flight batching of the 50-step sampler (SelftokPipeline.decode_stream).  `slots` requests share every model
+    evaluation, each at its own sampler step: the step state (timestep row of the modulation tables, visibility limit, dt) lives on the device,
+    one row per slot (csrc/decode_stream.hip), and the host only mirrors the step counters (schedule.SlotSchedule) to know the context rows
+    of the next step and who retires.  A step that retires nobody issues no host synchronisation and no host-to-device copy.
+      submit(ids, ...) -> ticket      the only place that copies from the host; StreamFull without a free slot
+      step() -> [(ticket, pixels [3, H, W][, latent [16, L, L]])]      the requests that have run their last step, in ticket order
+      drain() -> the same, stepping until the stream is empty
+    context="live": the model sees the context rows below the largest limit of a request in flight; "full": always all K rows (shape-static;
+    in f16x2 a request's bits then do not depend on its slot or its neighbours).  Idle slots are computed and discarded: the row count of
+    every Linear is fixed.  gemm='exact' is refused; one CFG scale per stream."""
+
+    def __init__(self, pipe: "SelftokPipeline", slots: int, uncond_scale: float = 1.0, max_steps: Optional[int] = None, context: str = "live",
+                 return_latent: bool = False):
+        self.pipe, self.dit = pipe, pipe.model.model
+        with torch.cuda.device(pipe.device), torch.no_grad():
+            self._build(int(slots), float(uncond_scale), max_steps, context, bool(return_latent))
+
+    def _check_mode(self):
+        if self.dit.gemm == "exact":
+            raise NotImplementedError("gemm='exact' decodes one visibility pattern per sampler call: a decode stream gives every slot its own key mask "
+                                      "(run the stream with gemm='fp32' / 'f16x2', or use decoding)")
+
+    def _build(self, slots, uncond_scale, max_steps, context, return_latent):
+        pipe, dit, dev = self.pipe, self.dit, self.pipe.device
+        self._check_mode()
+        if dit.renderer:
+            raise NotImplementedError("the renderer is one model pass, not a sampler: there is nothing to stream")
+        K, flow = pipe.K, pipe.flow
+        limit = np.minimum(np.asarray(pipe.k_table, dtype=np.int64) + 1, K)
+        self.sched = SlotSchedule(slots, limit, K, max_steps, context)
+        n, self.slots, self.K = self.sched.n_steps, slots, K
+        self.uncond_scale, self.guided, self.return_latent = uncond_scale, uncond_scale != 1.0, return_latent
+        self.x0_param = flow.parameterization == "x0"
+        self.see_xt = not self.guided                                            # p_sample_loop: context_see_xt and not guided (decoding passes True)
+        # the modulations of every scheduled timestep, once: [n, R] with R = 24 * 6H + 2H + 2H, and the same for the unconditional branch
+        def table(t_freq):
+            mx, mc, mf = dit.modulations(dit.time_embed(t_freq[:n].contiguous()), has_ctx=True)
+            return torch.cat(list(mx) + [mc, mf], dim=1).contiguous(), [int(t.shape[1]) for t in list(mx) + [mc, mf]]
+        with pipe._tunable_scope():
+            self.table, widths = table(flow.t_freq)
+            self.table_u = table(flow.t_freq_uncond)[0] if self.guided else None
+        first = np.concatenate([[0], np.cumsum(widths)[:-1]])
+        self.segs = np.ascontiguousarray(np.stack([first, widths], axis=1).astype(np.int32))
+        self.R = int(sum(widths))
+        self.limit = torch.from_numpy(limit[:n].astype(np.int32)).to(dev)
+        self.coef = torch.from_numpy(np.stack([flow.dt[:n], flow.scheduled_t[:n], flow.scheduled_t_prev[:n], np.zeros(n, np.float32)], axis=1)
+                                     .astype(np.float32)).contiguous().to(dev)
+        L, H, n_words = pipe.datasize // 8, W.DIT_HIDDEN, (K + 31) // 32
+        self.L = L
+        self.x = torch.zeros(slots, 16, L, L, device=dev)
+        self.noise0 = torch.zeros(slots, 16, L, L, device=dev)                   # the request's noise: an overflow restart starts from it again
+        self.ctx0 = torch.zeros(slots, K, H, device=dev)
+        self.cqkv0 = torch.zeros(slots, K, 3 * H, device=dev)                    # block 0's context QKV: step independent
+        self.pattern_words = torch.zeros(slots, n_words, dtype=torch.int32, device=dev)
+        self.kwords = torch.zeros(slots, n_words, dtype=torch.int32, device=dev)
+        self.step_dev = torch.full((slots,), -1, dtype=torch.int32, device=dev)
+        self.coef_rows = torch.zeros(slots, 4, device=dev)
+        self._requests = [None] * slots                                          # slot -> (ids, pattern): what a restart needs
+        self._fallback = set()                                                   # tickets that run on fp32 GEMMs after an overflow
+        self.mods = self._mod_views(torch.zeros(slots * self.R, device=dev))
+        self.mods_u = self._mod_views(torch.zeros(slots * self.R, device=dev)) if self.guided else None
+        k0 = int(pipe.diti.to_indices(flow.t_long[:1])[0])
+        self._ehs_mask = None if k0 >= K - 1 else (torch.arange(K, device=dev) <= k0)[None, :, None]
+        pipe._tune_linears(slots * (2 if self.guided else 1), pipe.k_table, (L // 2) ** 2)
+
+    def _mod_views(self, flat):
+        """(flat buffer, the `mods` of MMDiTGPU.core as views of it): segment s is the contiguous [slots, width_s] tensor at slots * first_s"""
+        views = [flat[self.slots * int(f): self.slots * int(f) + self.slots * int(w)].view(self.slots, int(w)) for f, w in self.segs]
+        return flat, (views[:-2], views[-2], views[-1])
+
+    free_slots = property(lambda self: self.sched.free_slots)
+    in_flight = property(lambda self: self.sched.in_flight)
+
+    def slot_of(self, ticket: int) -> int:
+        return self.sched.ticket.index(ticket)
+
+    # ---- admission -----------------------------------------------------------------------------------
+    def submit(self, ids, noise=None, ar_partial=None, super_mask=None, prefix_k=None) -> int:
+        """ids: [K] (or [1, K]) integer token ids; noise: [16, L, L] (default: one torch.randn(1, 16, L, L) draw from the global CPU generator);
+        ar_partial / super_mask ([K]) / prefix_k: the request's visibility, as `decoding` takes them for one sample.  -> ticket"""
+        with torch.cuda.device(self.pipe.device), torch.no_grad():
+            return self._submit(ids, noise, ar_partial, super_mask, prefix_k)
+
+    def _submit(self, ids, noise, ar_partial, super_mask, prefix_k):
+        self._check_mode()
+        K, pipe = self.K, self.pipe
+        if self.sched.free_slots == 0:
+            raise StreamFull(f"all {self.slots} slots are in flight: step() the stream until a request retires")
+        ids = ids.reshape(1, -1)
+        if ids.shape[1] != K:
+            raise ValueError(f"a request is one row of {K} token ids, got {ids.shape[1]}")
+        pattern, _ = request_pattern(K, 1, prefix_k, super_mask, ar_partial, False)
+        row = np.ones(K, dtype=bool) if pattern is None else (torch.as_tensor(pattern).cpu().numpy().reshape(-1) != 0)
+        if row.size != K:
+            raise ValueError(f"super_mask has {row.size} entries, the tokenizer has K = {K} tokens")
+        if prefix_k is not None:
+            row = row & (np.arange(K) < int(prefix_k))
+        xt = torch.randn(1, 16, self.L, self.L) if noise is None else torch.as_tensor(noise).reshape(1, 16, self.L, self.L)
+        pos = np.nonzero(row)[0]
+        ticket, slot = self.sched.submit(int(pos[0]) if pos.size else None)
+        self._requests[slot] = (ids, row)
+        self.noise0[slot:slot + 1].copy_(xt.to(self.pipe.device).float())
+        self.pattern_words[slot:slot + 1].copy_(ops.pack_key_mask(torch.from_numpy(row[None]).to(pipe.device)))
+        self._start(slot)
+        return ticket
+
+    def _start(self, slot: int) -> None:
+        """(re)start the slot's request at step 0 in the GEMM mode in force: its context, block 0's context QKV, its noise, step = 0"""
+        ids, _ = self._requests[slot]
+        dit = self.dit
+        with self.pipe._tunable_scope():
+            ehs = self.pipe._codes(ids)
+            if self._ehs_mask is not None:
+                ehs = ehs * self._ehs_mask
+            ctx0 = dit.embed_context(ehs)
+            self.ctx0[slot:slot + 1].copy_(ctx0)
+            self.cqkv0[slot:slot + 1].copy_(dit.block0_context_qkv(ctx0))
+        self.x[slot:slot + 1].copy_(self.noise0[slot:slot + 1])
+        self.step_dev[slot:slot + 1].fill_(0)
+
+    # ---- one sampler step of every slot --------------------------------------------------------------
+    def step(self):
+        with torch.cuda.device(self.pipe.device), torch.no_grad(), self.pipe._tunable_scope():
+            return self._step()
+
+    def _launch(self):
+        dit, K = self.dit, self.K
+        n_live = self.sched.n_live()
+        ops.stream_prepare(self.step_dev, self.limit, self.coef, self.pattern_words, self.table, self.table_u, self.segs, self.kwords, self.coef_rows,
+                           self.mods[0], None if self.mods_u is None else self.mods_u[0], K=K)
+        ctx = None if n_live == 0 else (self.ctx0 if n_live >= K else self.ctx0[:, :n_live].contiguous())
+        y = dit.core(dit.embed_image(self.x), None, ctx, self.see_xt, cqkv0=self.cqkv0 if n_live > 0 else None, mods=self.mods[1],
+                     kmask=self.kwords if n_live > 0 else None)
+        yu = dit.core(dit.embed_image(self.x), None, None, False, mods=self.mods_u[1]) if self.guided else None
+        ops.unpatchify_cfg_euler_rows(y, yu, self.x, self.coef_rows, self.step_dev, cfg_scale=self.uncond_scale, x0_param=self.x0_param)
+
+    def _step(self):
+        self._check_mode()
+        dit = self.dit
+        if self.sched.in_flight == 0:
+            return []
+        mode = (dit.gemm, dit.attention, dit.splitk)
+        if self._fallback and mode[0] in dit.SPLIT_MODES:
+            dit.set_gemm("fp32")
+            try:
+                self._launch()
+            finally:
+                dit.set_gemm(mode[0], attention=mode[1], splitk=mode[2])
+        else:
+            self._launch()
+        done = self.sched.advance()
+        if not done:
+            return []
+        # a retirement: the host waits here anyway, so this is where the sticky fp16-range flag of the split modes is read (_checked's contract)
+        if mode[0] in dit.SPLIT_MODES and int(dit.overflow.item()) != 0:
+            print(f"[selftok] {mode[0]} GEMM: activation outside the fp16 range -> restarting the {self.sched.in_flight} requests in flight with fp32 GEMMs")
+            dit.overflow.zero_()
+            dit.set_gemm("fp32")
+            try:
+                for slot in self.sched.restart():
+                    self._fallback.add(self.sched.ticket[slot])
+                    self._start(slot)
+            finally:
+                dit.set_gemm(mode[0], attention=mode[1], splitk=mode[2])
+            return []
+        slots = [s for _, s in done]
+        latents = self.x[slots[0]:slots[0] + 1].clone() if len(slots) == 1 else torch.cat([self.x[s:s + 1] for s in slots])
+        pixels = self.pipe._to_pixels(latents)                                   # the retirements of one step share one VAE call
+        out = []
+        for j, (ticket, slot) in enumerate(done):
+            self.sched.retire(slot)
+            self.step_dev[slot:slot + 1].fill_(-1)
+            self._requests[slot] = None
+            self._fallback.discard(ticket)
+            out.append((ticket, pixels[j], latents[j]) if self.return_latent else (ticket, pixels[j]))
+        return out
+
+    def drain(self):
+        out = []
+        while self.in_flight:
+            out.extend(self.step())
+        return out

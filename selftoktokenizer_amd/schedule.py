@@ -189,3 +189,84 @@ def request_pattern(K: int, B: int, prefix_k=None, super_mask=None, ar_partial=N
         raise ValueError(f"ar_partial must be in [0, {K}]")
     sm = tokens.suffix_mask(K, m)
     return (sm[0], mask_batched) if bool((m == m[0]).all()) else (sm, True)
+
+
+# ---- decode stream: which slot is at which sampler step (pipeline.DecodeStream; tests/test_decode_stream_cpu.py) ----
+class StreamFull(RuntimeError):
+    """`submit` on a stream without a free slot: step the stream (a retirement frees a slot) and submit again"""
+
+
+class SlotSchedule:
+    """The host's mirror of a decode stream: `slots` slots, each idle (step -1) or at sampler step 0 .. n_steps - 1 of its own request.
+    Pure host logic.  `limit[i]` = min(k_table[i] + 1, K): the keys a request at step i may see; a request runs n_steps = min(max_steps,
+    len(limit)) steps.  Tickets count up from 0 in submit order; a request takes the LOWEST free slot."""
+    CONTEXTS = ("live", "full")
+
+    def __init__(self, slots: int, limit, K: int, max_steps: Optional[int] = None, context: str = "live"):
+        if int(slots) < 1:
+            raise ValueError(f"slots = {slots}: expected at least 1")
+        if context not in self.CONTEXTS:
+            raise ValueError(f"context {context!r}: expected one of {self.CONTEXTS}")
+        self.limit = np.asarray(limit, dtype=np.int64).copy()
+        if self.limit.ndim != 1 or self.limit.size < 1 or self.limit.min() < 0 or self.limit.max() > K:
+            raise ValueError(f"limit: expected one value in [0, {K}] per step")
+        if max_steps is not None and int(max_steps) < 1:
+            raise ValueError(f"max_steps = {max_steps}: expected None or at least 1")
+        self.slots, self.K, self.context = int(slots), int(K), context
+        self.n_steps = self.limit.size if max_steps is None else min(int(max_steps), self.limit.size)
+        self.step = [-1] * self.slots            # the device's `step`, mirrored
+        self.ticket = [None] * self.slots
+        self.first_visible = [None] * self.slots  # lowest position the slot's pattern shows (None: none at all)
+        self._next = 0
+
+    @property
+    def free_slots(self) -> int:
+        return sum(t is None for t in self.ticket)
+
+    @property
+    def in_flight(self) -> int:
+        return self.slots - self.free_slots
+
+    def active(self):
+        """the occupied slots in ticket (= submit) order"""
+        return sorted((s for s in range(self.slots) if self.ticket[s] is not None), key=lambda s: self.ticket[s])
+
+    def submit(self, first_visible: Optional[int] = 0):
+        """-> (ticket, slot).  `first_visible`: the lowest position of the request's visibility pattern (0 without a pattern; None for an
+        empty pattern)"""
+        for s in range(self.slots):
+            if self.ticket[s] is None:
+                self.ticket[s], self.step[s], self.first_visible[s] = self._next, 0, first_visible
+                self._next += 1
+                return self.ticket[s], s
+        raise StreamFull(f"all {self.slots} slots are in flight: step() the stream until a request retires")
+
+    def n_live(self) -> int:
+        """context rows of the NEXT step: the largest limit[step] of an occupied slot ('full': K), 0 when no occupied slot sees a key"""
+        occ = [s for s in range(self.slots) if self.ticket[s] is not None]
+        if not occ:
+            return 0
+        if self.context == "full":
+            return self.K
+        sees = any(self.first_visible[s] is not None and self.first_visible[s] < self.limit[self.step[s]] for s in occ)
+        return int(max(self.limit[self.step[s]] for s in occ)) if sees else 0
+
+    def advance(self):
+        """one stream step has been launched: every occupied slot moves on; -> [(ticket, slot)] of the requests that have now run their
+        n_steps steps, in ticket order.  They keep their slots until `retire`."""
+        done = []
+        for s in self.active():
+            self.step[s] += 1
+            if self.step[s] >= self.n_steps:
+                done.append((self.ticket[s], s))
+        return done
+
+    def retire(self, slot: int) -> None:
+        self.ticket[slot], self.step[slot], self.first_visible[slot] = None, -1, None
+
+    def restart(self):
+        """every occupied slot back to step 0 (the overflow fallback of the split GEMM modes) -> the slots, in ticket order"""
+        occ = self.active()
+        for s in occ:
+            self.step[s] = 0
+        return occ
