@@ -374,6 +374,40 @@ int selftok_unpatchify_cfg_euler_rows_f32(const float* y_cond, const float* y_un
                                           const int* step, int* step_out, int B, int C, int hp, int wp, float cfg_scale, int x0_param,
                                           hipStream_t stream);
 
+/* ---- token statistics on [N, K] matrices of code ids (csrc/token_stats.hip) ----------------------------------------------------------
+ * Code usage and perplexity, agreement of two tokenisations, the nearest sequence of a set.  Integer arithmetic, one fp64 entropy.  Every
+ * entry is stateless and capturable, allocates and synchronises nothing, and decides every refusal on the host before any launch
+ * (SELFTOK_EINVAL with a message; the workspace queries return 0 with the message set): a refused call leaves its outputs untouched.
+ *
+ * token_count: ids of id_bytes 2 (uint16), 4 (int32) or 8 (int64); id (r, k) sits at element r * row_stride + k * elem_stride (strides in
+ *   ELEMENTS, >= 0).  counts[k * C + id] += 1 (uint32 [K, C], plain global atomics, accumulating: the caller zeroes once); an id outside
+ *   [0, C) is not counted, writes nothing and adds 1 to bad[0].  n_rows * K and K * C below 2^31.  n_rows == 0: no launch.
+ * token_census: counts [K, C] -> out double [K + 1, 5], one row per position and row K for the POOLED counts (the uint64 column sums over
+ *   the positions): (n, used, H, H_ref, max_count), p = count / n, n the sum, used the codes with count > 0, H = -sum p ln p (a zero count
+ *   adds exactly nothing), H_ref = -sum p ln(p + 1e-10).  fp64 in a fixed order (csrc/token_stats.hip states it), no atomics: the same
+ *   bits every run.  A row with n == 0 is (0, 0, 0, 0, 0).  Workspace: the pooled counts, C * 8 bytes.
+ * token_to_u16: the same ids -> dense uint16 out [n_rows, K]; an id outside [0, 65535] writes 0 and adds 1 to bad[0].
+ * token_agree: a, b dense uint16 [n_rows, K], positions [k_lo, k_hi), 0 <= k_lo <= k_hi <= K <= 65535, n_rows <= 256 * 65535:
+ *   match_pos[k] += 1 where the rows agree at k (uint32 [K], accumulating; positions outside the range untouched); per row n_diff, the
+ *   lowest differing index first_diff (K if none) and the highest last_diff (-1 if none), all int32.
+ * token_nearest: q [M, K], ref [N, K] dense uint16 -> best_match[i] = the largest number of equal positions in [k_lo, k_hi) over the
+ *   reference rows, best_idx[i] = the lowest index that attains it (int32).  exclude_self == 0: every row is a candidate; exclude_self
+ *   == 1 + o (o >= 0) skips j == i + o -- 1 for a set searched against itself, 1 + the chunk's first row when the queries are a chunk of
+ *   it.  No candidate (N == 0, or the only row excluded): best_match -1, best_idx 0.  `split`: the number of reference splits (0 =
+ *   automatic, clamped to min(64, ceil(N / 64))); the outputs never depend on it.  Workspace: one 64-bit key per split and query.
+ *   M == 0 returns 0 without a launch. */
+int selftok_token_count(const void* ids, int id_bytes, long n_rows, int K, int C, long row_stride, long elem_stride, unsigned* counts, unsigned* bad,
+                        hipStream_t stream);
+size_t selftok_token_census_workspace_bytes(int K, int C);
+int selftok_token_census(const unsigned* counts, int K, int C, double* out, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int selftok_token_to_u16(const void* ids, int id_bytes, long n_rows, int K, long row_stride, long elem_stride, unsigned short* out, unsigned* bad,
+                         hipStream_t stream);
+int selftok_token_agree(const unsigned short* a, const unsigned short* b, int n_rows, int K, int k_lo, int k_hi, unsigned* match_pos, int* n_diff,
+                        int* first_diff, int* last_diff, hipStream_t stream);
+size_t selftok_token_nearest_workspace_bytes(int M, int N);
+int selftok_token_nearest(const unsigned short* q, int M, const unsigned short* ref, int N, int K, int k_lo, int k_hi, int exclude_self, int split, int* best_match,
+                          int* best_idx, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

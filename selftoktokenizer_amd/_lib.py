@@ -135,6 +135,13 @@ EXT_SIGNATURES = {
     "selftok_kid_sums_f32": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "selftok_stream_prepare": (_i, [_vp] * 7 + [_i] + [_vp] * 4 + [_i, _i, _i, _l, _vp]),
     "selftok_unpatchify_cfg_euler_rows_f32": (_i, [_vp] * 7 + [_i, _i, _i, _i, _f, _i, _vp]),
+    "selftok_token_count": (_i, [_vp, _i, _l, _i, _i, _l, _l, _vp, _vp, _vp]),
+    "selftok_token_census_workspace_bytes": (_sz, [_i, _i]),
+    "selftok_token_census": (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "selftok_token_to_u16": (_i, [_vp, _i, _l, _i, _l, _l, _vp, _vp, _vp]),
+    "selftok_token_agree": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "selftok_token_nearest_workspace_bytes": (_sz, [_i, _i]),
+    "selftok_token_nearest": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -102,7 +102,9 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     device route; ssim_skimage_signed: on [-1, 1] data with data_range 2 (default) or on [0, 1] data with data_range 1.  Every decoder's dict gains
     `ssim_skimage_mean` / `ssim_skimage_each`, `metric_definition["ssim_skimage"]` states window, moments, range and quantisation; metrics_u8 applies.
     `lpips=` may also be a sequence of LpipsNets of different backbones: each then writes `lpips_<net>_mean` / `lpips_<net>_each` and
-    `metric_definition["lpips_<net>"]`; one network given on its own writes the `lpips_*` keys above."""
+    `metric_definition["lpips_<net>"]`; one network given on its own writes the `lpips_*` keys above.
+    "tokens" (beside any of the above): adds `token_census`, tokenstats.TokenCensus.summary() of the ids this RANK encoded anyway (code-book usage, perplexity of
+    the pooled counts and the reference's 1e-10 form, per-position extremes, dead codes), counted on the device; every other key is what a run without it gives."""
     lpips_nets = None                                        # a sequence of networks: keys by backbone name
     if lpips is not None and not callable(lpips):
         lpips_nets = list(lpips)
@@ -113,7 +115,8 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     with_sk = "ssim_skimage" in metrics
     with_fid = "rfid" in metrics and fid is not None
     with_pr = "precision_recall" in metrics and fid is not None
-    bad = [m for m in metrics if m not in ("psnr", "ssim", "ssim_skimage") and not (m == "lpips" and with_lpips) and not (m == "rfid" and with_fid) and not (m == "precision_recall" and with_pr)]
+    with_tokens = "tokens" in metrics
+    bad = [m for m in metrics if m not in ("psnr", "ssim", "ssim_skimage", "tokens") and not (m == "lpips" and with_lpips) and not (m == "rfid" and with_fid) and not (m == "precision_recall" and with_pr)]
     if bad or not metrics:
         raise ValueError(f"metrics {tuple(metrics)!r}: expected a non-empty subset of ('psnr', 'ssim')" + (", or 'lpips' together with lpips=<LpipsNet>" if "lpips" in bad else "")
                          + (", or 'rfid' together with fid=<InceptionNet>" if "rfid" in bad else "")
@@ -138,12 +141,18 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
     feats = {d: [] for d in decoders}            # "rfid": pool3 features [b, 2048] fp32 per batch, the originals under None
     feats[None] = []
     ids_all = []
+    census = None
     for b0 in range(lo, hi, batch):
         b1 = min(b0 + batch, hi)
         imgs = load_batch(b0, b1).to(pipe.device)
         tokens = pipe.encoding(imgs, device=pipe.device)
         ids = tokens.detach().cpu().numpy()                       # the reference round-trips the ids through a host .npy (test.py:38-39)
         ids_all.append(ids)
+        if with_tokens:
+            if census is None:
+                from .tokenstats import TokenCensus
+                census = TokenCensus(tokens.shape[-1], int(pipe.model.encoder.codebook.shape[0]), pipe.device)
+            census.update(tokens.detach())
         if with_feats:
             feats[None].append(fid.pool3(imgs, signed=True, quantize=metrics_u8))
         for d in decoders:
@@ -219,6 +228,8 @@ def evaluate(pipe, load_batch: Callable[[int, int], torch.Tensor], n_images: int
         if with_pr:
             out["metric_definition"]["precision_recall"] = dict(GM.GEN_METRICS_DEFINITION, weights=fid.source, resized=bool(fid.resize), n=int(n_images))
     out["token_ids_first_image"] = ids_all[0][0, :8].tolist() if ids_all else []
+    if census is not None:
+        out["token_census"] = dict(census.summary(), dead_codes=int(census.dead_codes().size), shard=[int(lo), int(hi)])
     return out
 
 

@@ -1795,3 +1795,155 @@ def unpatchify_cfg_euler_rows(y_cond, y_uncond, x, coef_rows, step, *, cfg_scale
     _lib.check(_lib.load().selftok_unpatchify_cfg_euler_rows_f32(_p(y_cond), _p(y_uncond), _p(x), _p(x_out), _p(coef_rows), _p(step), _p(step_out), B, C, hp, wp,
                                                                  float(cfg_scale), int(bool(x0_param)), _stream()), "selftok_unpatchify_cfg_euler_rows_f32")
     return x_out, step_out
+
+
+# ----------------------------------------------------------------------------------------------
+# token statistics (csrc/token_stats.hip): code counts, census, agreement, nearest sequence
+# ----------------------------------------------------------------------------------------------
+_TOKEN_ID_BYTES = {torch.uint16: 2, torch.int32: 4, torch.int64: 8}
+
+
+def _token_ids(what: str, ids: torch.Tensor):
+    """ids [..., K] of dtype uint16 / int32 / int64, any strides -> (tensor, n_rows, K, row_stride, elem_stride) without a copy where the leading
+    dimensions collapse into one row stride (a [N, K] view of any strides always does); otherwise one contiguous copy"""
+    if ids.dtype not in _TOKEN_ID_BYTES or ids.dim() < 1:
+        raise _lib.SelftokHipError(f"{what}: expected uint16, int32 or int64 ids [..., K], got {ids.dtype} {tuple(ids.shape)}")
+    K = ids.shape[-1]
+    if ids.dim() == 1:
+        ids = ids.unsqueeze(0)
+    elif ids.dim() > 2:
+        lead = ids.shape[:-1]
+        n = 1
+        for v in lead:
+            n *= v
+        try:
+            ids = ids.view(n, K)                                   # strided views that still collapse stay views
+        except RuntimeError:
+            ids = ids.reshape(n, K)
+    n_rows = ids.shape[0]
+    rs, es = (ids.stride(0), ids.stride(1)) if n_rows and K else (K, 1)
+    if rs < 0 or es < 0 or (n_rows > 1 and rs == 0):
+        ids = ids.contiguous()
+        rs, es = K, 1
+    return ids, n_rows, K, rs, es
+
+
+def _token_u32(what: str, name: str, t: torch.Tensor, shape):
+    if t.dtype not in (torch.int32, torch.uint32) or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise _lib.SelftokHipError(f"{what}: `{name}` must be a contiguous 32-bit integer tensor {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def token_count(ids: torch.Tensor, counts: torch.Tensor, bad: torch.Tensor) -> None:
+    """counts[k, id] += 1 for every row and position of ids [..., K] (uint16 / int32 / int64, strided views counted in place: column 0 of an
+    `encoding_topk` result needs no copy).  counts: 32-bit [K, C], bad: 32-bit [1], both ACCUMULATING (uint32 arithmetic); an id outside [0, C) only adds 1
+    to bad.  No synchronisation."""
+    _need_cuda(ids, counts, bad)
+    if counts.dim() != 2:
+        raise _lib.SelftokHipError(f"token_count: `counts` must be [K, C], got {tuple(counts.shape)}")
+    ids, n_rows, K, rs, es = _token_ids("token_count", ids)
+    _token_u32("token_count", "counts", counts, (K, counts.shape[1]))
+    _token_u32("token_count", "bad", bad, (1,))
+    lib = _lib.load()
+    _lib.check(lib.selftok_token_count(_p(ids) if n_rows else None, _TOKEN_ID_BYTES[ids.dtype], n_rows, K, counts.shape[1], rs, es, _p(counts), _p(bad), _stream()),
+               "selftok_token_count")
+
+
+def token_census(counts: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """counts 32-bit [K, C] -> fp64 [K + 1, 5]: (n, used, H, H_ref, max_count) per position, row K for the pooled counts (uint64 column sums).  Entropies in nats,
+    fp64 in a fixed order: the same bits every run."""
+    _need_cuda(counts, out, workspace)
+    if counts.dim() != 2:
+        raise _lib.SelftokHipError(f"token_census: `counts` must be [K, C], got {tuple(counts.shape)}")
+    K, C = counts.shape
+    _token_u32("token_census", "counts", counts, (K, C))
+    lib = _lib.load()
+    need = lib.selftok_token_census_workspace_bytes(K, C)
+    if need == 0:
+        _lib.check(-1, "selftok_token_census_workspace_bytes")
+    ws = torch.empty(need // 8, dtype=torch.int64, device=counts.device) if workspace is None else workspace
+    if out is None:
+        out = torch.empty(K + 1, 5, dtype=torch.float64, device=counts.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (K + 1, 5) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"token_census: `out` must be a contiguous float64 [{K + 1}, 5], got {out.dtype} {tuple(out.shape)}")
+    _lib.check(lib.selftok_token_census(_p(counts), K, C, _p(out), _p(ws), ws.numel() * ws.element_size(), _stream()), "selftok_token_census")
+    return out
+
+
+def token_to_u16(ids: torch.Tensor, bad: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ids [..., K] (uint16 / int32 / int64, any strides) -> dense uint16 [n_rows, K]; an id outside [0, 65535] becomes 0 and adds 1 to bad[0] (32-bit [1],
+    accumulating; allocated zeroed when None and then dropped: pass one to see it)."""
+    _need_cuda(ids, bad, out)
+    ids, n_rows, K, rs, es = _token_ids("token_to_u16", ids)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=ids.device)
+    _token_u32("token_to_u16", "bad", bad, (1,))
+    if out is None:
+        out = torch.empty(n_rows, K, dtype=torch.uint16, device=ids.device)
+    elif out.dtype != torch.uint16 or tuple(out.shape) != (n_rows, K) or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"token_to_u16: `out` must be a contiguous uint16 [{n_rows}, {K}], got {out.dtype} {tuple(out.shape)}")
+    lib = _lib.load()
+    _lib.check(lib.selftok_token_to_u16(_p(ids) if n_rows else None, _TOKEN_ID_BYTES[ids.dtype], n_rows, K, rs, es, _p(out) if n_rows else None, _p(bad), _stream()),
+               "selftok_token_to_u16")
+    return out
+
+
+def _token_dense(what: str, name: str, t: torch.Tensor) -> torch.Tensor:
+    if t.dtype != torch.uint16 or t.dim() != 2 or not t.is_contiguous():
+        raise _lib.SelftokHipError(f"{what}: `{name}` must be a dense uint16 [rows, K] tensor (ops.token_to_u16 makes one), got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _token_range(what: str, K: int, k_range):
+    k_lo, k_hi = (0, K) if k_range is None else (int(k_range[0]), int(k_range[1]))
+    if not 0 <= k_lo <= k_hi <= K:
+        raise _lib.SelftokHipError(f"{what}: k_range must satisfy 0 <= k_lo <= k_hi <= K = {K}, got ({k_lo}, {k_hi})")
+    return k_lo, k_hi
+
+
+def token_agree(a: torch.Tensor, b: torch.Tensor, k_range=None, match_pos: Optional[torch.Tensor] = None):
+    """a, b dense uint16 [N, K] -> (match_pos 32-bit [K], n_diff, first_diff, last_diff int32 [N]) over the positions k_range = (k_lo, k_hi), default every one:
+    match_pos[k] += the rows that agree at k (accumulating when passed in, zeroed when allocated here), first_diff K and last_diff -1 for equal rows."""
+    _need_cuda(a, b, match_pos)
+    a, b = _token_dense("token_agree", "a", a), _token_dense("token_agree", "b", b)
+    if a.shape != b.shape:
+        raise _lib.SelftokHipError(f"token_agree: a and b must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    N, K = a.shape
+    k_lo, k_hi = _token_range("token_agree", K, k_range)
+    if match_pos is None:
+        match_pos = torch.zeros(K, dtype=torch.int32, device=a.device)
+    _token_u32("token_agree", "match_pos", match_pos, (K,))
+    n_diff, first, last = (torch.empty(N, dtype=torch.int32, device=a.device) for _ in range(3))
+    lib = _lib.load()
+    _lib.check(lib.selftok_token_agree(_p(a) if N else None, _p(b) if N else None, N, K, k_lo, k_hi, _p(match_pos), _p(n_diff) if N else None, _p(first) if N else None,
+                                       _p(last) if N else None, _stream()), "selftok_token_agree")
+    return match_pos, n_diff, first, last
+
+
+def token_nearest(q: torch.Tensor, ref: torch.Tensor, k_range=None, exclude_self: int = 0, *, split: int = 0, out_match: Optional[torch.Tensor] = None,
+                  out_idx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """q [M, K], ref [N, K] dense uint16 -> (best_match, best_idx) int32 [M]: the largest number of equal positions in k_range over the reference rows and the
+    lowest index that attains it; (-1, 0) without a candidate.  exclude_self: 0 = every row is a candidate, 1 + o skips j == i + o (1: the set against itself).
+    split: launch-shape override, never visible in the result.  M == 0: empty tensors, no launch."""
+    _need_cuda(q, ref, out_match, out_idx, workspace)
+    q, ref = _token_dense("token_nearest", "q", q), _token_dense("token_nearest", "ref", ref)
+    M, K = q.shape
+    N = ref.shape[0]
+    if ref.shape[1] != K:
+        raise _lib.SelftokHipError(f"token_nearest: q and ref must have one K, got {tuple(q.shape)} and {tuple(ref.shape)}")
+    k_lo, k_hi = _token_range("token_nearest", K, k_range)
+    lib = _lib.load()
+    need = lib.selftok_token_nearest_workspace_bytes(M, N)
+    if need == 0:
+        _lib.check(-1, "selftok_token_nearest_workspace_bytes")
+    ws = torch.empty(need // 8, dtype=torch.int64, device=q.device) if workspace is None else workspace
+    outs = []
+    for name, t in (("out_match", out_match), ("out_idx", out_idx)):
+        if t is None:
+            t = torch.empty(M, dtype=torch.int32, device=q.device)
+        elif t.dtype != torch.int32 or tuple(t.shape) != (M,) or not t.is_contiguous():
+            raise _lib.SelftokHipError(f"token_nearest: `{name}` must be a contiguous int32 [{M}], got {t.dtype} {tuple(t.shape)}")
+        outs.append(t)
+    if M:
+        _lib.check(lib.selftok_token_nearest(_p(q), M, _p(ref) if N else None, N, K, k_lo, k_hi, int(exclude_self), int(split), _p(outs[0]), _p(outs[1]), _p(ws),
+                                             ws.numel() * ws.element_size(), _stream()), "selftok_token_nearest")
+    return outs[0], outs[1]

@@ -12,14 +12,18 @@ and, for k >= 2, adds the near-tie census of the top-1 / top-2 margins to the JS
 Augmented runs: --crops five | ten takes torchvision's FiveCrop / TenCrop(data_size) of the image resized to --resize R (shorter side, default
 data_size), --flip adds the mirror image of every view; each view is the tensor torchvision gives on the PIL image, bit for bit
 (csrc/image_views.hip, every file still crosses to the GPU once).  With more than one view per image the id file is int64 [n, views, K] (and the
-top-k arrays [n, views, K, k]), views in torchvision's order, and the JSON line names the recipe; --batch counts images, not views."""
+top-k arrays [n, views, K, k]), views in torchvision's order, and the JSON line names the recipe; --batch counts images, not views.
+
+--stats adds `token_census` to the JSON line (selftoktokenizer_amd.tokenstats.TokenCensus of this rank's ids: code-book usage, perplexity, dead codes)
+and, with more than one view per image, `view_agreement`: every view against view 0 (match rate, mean number of differing positions).  Both accumulate
+on the device, one read at the end; the id files are the same bytes with and without it."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from mimogpt.infer.infer_utils import parse_args_from_yaml
 from mimogpt.infer.SelftokPipeline import SelftokPipeline
-from selftoktokenizer_amd import dist as D, evaluate as E, preprocess, synth, tokens, weights as W
+from selftoktokenizer_amd import dist as D, evaluate as E, ops, preprocess, synth, tokens, tokenstats, weights as W
 from selftoktokenizer_amd.config import default_config
 
 ap = argparse.ArgumentParser()
@@ -40,6 +44,7 @@ ap.add_argument("--crops", default="center", choices=["center", "five", "ten"], 
 ap.add_argument("--resize", type=int, default=0, help="R >= data_size: shorter side of the resize before the crops (default: data_size)")
 ap.add_argument("--flip", action="store_true", help="also emit the mirror image of every view")
 ap.add_argument("--preprocess", default="reference", choices=["reference", "bicubic", "adm"], help="the reference's bilinear Resize; bicubic Resize (the views likewise); or the ADM protocol center_crop_arr, which is one centre crop per image (no --crops / --resize / --flip)")
+ap.add_argument("--stats", action="store_true", help="add the code census of the ids (usage, perplexity) and, with several views per image, their agreement with view 0 to the JSON line")
 ap.add_argument("--out", default=None, help="prefix of the id files; nothing is written without it")
 a = ap.parse_args()
 if not 0 <= a.topk <= 8:
@@ -83,6 +88,9 @@ else:
 loader = preprocess.DeviceLoader(a.data_size, dev, dtype=torch.bfloat16, workers=a.workers, preprocess=a.preprocess)
 loader.timing = True
 topk_ids, topk_scores = [], []
+census = tokenstats.TokenCensus(K, int(pipe.model.encoder.codebook.shape[0]), dev) if a.stats else None
+view_match = torch.zeros(K, dtype=torch.int32, device=dev)           # rows of views 1.. that agree with view 0, per position
+view_diff = torch.zeros(1, dtype=torch.int64, device=dev)            # differing positions over those rows
 ids, split, marks = [], {"host_decode_s": 0.0, "pack_s": 0.0, "h2d_ms": 0.0, "resize_kernels_ms": 0.0, "encode_ms": 0.0}, []
 torch.cuda.synchronize()
 t0 = time.perf_counter()
@@ -96,6 +104,13 @@ for batch in (loader.batches(items, a.batch, views=views) if views else loader.b
         tok = pipe.encoding(batch, device=dev)
     e3.record()
     marks.append(ev + (e3,))
+    if a.stats:                                                      # after the encode mark: on the device, nothing read back
+        census.update(tok)
+        if nviews > 1:
+            t3 = tok.reshape(-1, nviews, K)
+            first = ops.token_to_u16(t3[:, :1].expand(-1, nviews - 1, -1).reshape(-1, K))
+            rest = ops.token_to_u16(t3[:, 1:].reshape(-1, K))
+            view_diff += ops.token_agree(first, rest, match_pos=view_match)[1].sum()
     split["host_decode_s"] += lt["decode_s"]; split["pack_s"] += lt["pack_s"]
     ids.append(tok.cpu().numpy())
     if a.topk:
@@ -127,6 +142,16 @@ if a.topk:
 if views:
     extra.update({"crops": a.crops, "resize": R, "flip": bool(a.flip), "views_per_image": nviews, "views": n * nviews,
                   "recipe": f"Resize({R}) -> {dict(center='CenterCrop', five='FiveCrop', ten='TenCrop')[a.crops]}({a.data_size})" + (" + mirror images" if a.flip else "")})
+if a.stats:
+    extra["rank0_token_census"] = census.summary()
+    extra["rank0_token_census"]["dead_codes"] = int(census.dead_codes().size)
+    if a.out:
+        census.save(f"{a.out}.rank{rank}.census.npz")               # ranks combine offline: TokenCensus.load(...).merge(...)
+    if nviews > 1:
+        rows = int(ids.shape[0]) * (nviews - 1)
+        match = int(view_match.cpu().numpy().view(np.uint32).astype(np.int64).sum())
+        extra["rank0_view_agreement"] = {"against": "view 0", "rows": rows, "match_rate": match / (rows * K) if rows else None,
+                                         "mean_n_diff": int(view_diff.item()) / rows if rows else None}
 slowest = D.max_over_ranks(wall, dev)
 D.barrier()
 if rank == 0:
