@@ -3,9 +3,10 @@
 // (eight fmaf chains by k mod 16, a fixed fp32 tree, one bias addition, the optional ReLU) and the same packed weight layout
 // ([KP][CoutP], row k = (kh * KW + kw) * Cin + ci).  The geometry is general: KH x KW kernel, pad_h / pad_w per axis, and an output row
 // of `ldo` floats of which this convolution writes the Cout channels from `co_off` on -- a branch of a concatenated map writes its own
-// slice and nothing else.  The LPIPS entry passes pad_h = pad_w, ldo = Cout, co_off = 0.
+// slice and nothing else.  The LPIPS entry passes pad_h = pad_w, ldo = Cout, co_off = 0.  The host side of both entries is conv_plan below.
 #pragma once
 #include "common.h"
+#include <stdio.h>
 
 namespace selftok {
 namespace conv_f32 {
@@ -127,6 +128,47 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a)
 
 // output side of a convolution / pool, 0 when there is no output pixel
 inline int out_side(int in, int k, int stride, int pad) { const long s = (long)in + 2l * pad - k; return s < 0 ? 0 : (int)(s / stride + 1); }
+
+// the host side of a convolution entry `name` (its name in the messages): every refusal -- geometry, slice, the element counts of input, output map
+// and packed weight below 2^31, alignment, the grid limit -- then the ConvArgs and the grid of its `*_conv_kernel<VEC>`, VEC = (Cin % 4 == 0).
+// false with the error set.
+inline bool conv_plan(const char* name, const float* in, const float* packed, const float* bias, float* out, int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                      int stride, int pad_h, int pad_w, int ldo, int co_off, int relu, ConvArgs* a, dim3* grid)
+{
+    char msg[320];
+    auto fail = [&] { set_last_error(msg); return false; };
+    constexpr long LIM = 1l << 31;
+    if (!in || !packed || !out) { snprintf(msg, sizeof msg, "%s: null pointer", name); return fail(); }
+    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1 || pad_h < 0 || pad_h >= KH || pad_w < 0 || pad_w >= KW) {
+        snprintf(msg, sizeof msg, "%s: need N, H, W, Cin, Cout, KH, KW, stride >= 1, 0 <= pad_h < KH and 0 <= pad_w < KW, got N %d, %d x %d, Cin %d, Cout %d, "
+                 "%d x %d, stride %d, pad %d, %d", name, N, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w);
+        return fail();
+    }
+    if (co_off < 0 || (long)ldo < (long)co_off + Cout) {
+        snprintf(msg, sizeof msg, "%s: the slice needs co_off >= 0 and ldo >= co_off + Cout, got ldo %d, co_off %d, Cout %d", name, ldo, co_off, Cout);
+        return fail();
+    }
+    const int OH = out_side(H, KH, stride, pad_h), OW = out_side(W, KW, stride, pad_w);
+    if (OH < 1 || OW < 1) {
+        snprintf(msg, sizeof msg, "%s: %d x %d input has no output pixel under a %d x %d kernel with pad %d, %d", name, H, W, KH, KW, pad_h, pad_w);
+        return fail();
+    }
+    const long kk = (long)KH * KW;
+    if (kk >= LIM / Cin || (long)H * W >= LIM / Cin || (long)N >= LIM / ((long)H * W * Cin) || (long)OH * OW >= LIM / ldo ||
+        (long)N >= LIM / ((long)OH * OW * ldo) || ((kk * Cin + KT - 1) / KT * KT) >= LIM / ((Cout + BN - 1) / BN * BN)) {
+        snprintf(msg, sizeof msg, "%s: input, output map and packed weight element counts must stay below 2^31, got N %d, %d x %d, Cin %d, Cout %d, %d x %d, ldo %d",
+                 name, N, H, W, Cin, Cout, KH, KW, ldo);
+        return fail();
+    }
+    if (((uintptr_t)in & 15) != 0 || ((uintptr_t)packed & 15) != 0 || ((uintptr_t)out & 3) != 0 || ((uintptr_t)bias & 3) != 0) {
+        snprintf(msg, sizeof msg, "%s: in and packed must be 16-byte aligned, out and bias 4-byte aligned", name); return fail();
+    }
+    *a = ConvArgs{in, packed, bias, out, H, W, Cin, OH, OW, Cout, (Cout + BN - 1) / BN * BN, KH, KW, stride, pad_h, pad_w, KH * KW * Cin,
+                  (KH * KW * Cin + KT - 1) / KT * KT, relu != 0, ldo, co_off, (long)N * OH * OW};
+    *grid = dim3((unsigned)((a->M + BM - 1) / BM), (unsigned)(a->CoutP / BN));
+    if (grid->y > 65535u) { snprintf(msg, sizeof msg, "%s: Cout above 64 * 65535", name); return fail(); }
+    return true;
+}
 
 }  // namespace conv_f32
 }  // namespace selftok

@@ -3,14 +3,13 @@
 // torch-CPU fp64 and the statistics in numpy fp64.  Activations are channels-last fp32 [N, H, W, C]; a block's branches write their
 // channel slices of ONE concatenated map (row stride `ldo`, first channel `co_off`): there is no concatenation pass.
 //
-// Convolution: csrc/conv_f32_shared.h's tile body, the one selftok_lpips_conv2d_f32 runs -- the arithmetic of record at the top of
-// csrc/lpips.hip (eight fmaf chains by k mod 16 on v_mfma_f32_32x32x2_f32, fixed tree, one bias addition, ReLU), with pad_h / pad_w per
-// axis and the slice.
-// Pool (3 x 3): max / stride 2 / no padding, max / stride 1 / pad 1 (a padding tap never takes part), average / stride 1 / pad 1 with
-//   the number of in-image taps as the divisor: s = +0.0f, s = s + tap for the in-image taps in (kh, kw) order, then s / (float)count.
-//   A NaN in a window is the window's result.
+// Convolution: csrc/conv_f32_shared.h's tile body and host side, the ones selftok_lpips_conv2d_f32 runs -- the arithmetic of record at the
+// top of csrc/lpips.hip (eight fmaf chains by k mod 16 on v_mfma_f32_32x32x2_f32, fixed tree, one bias addition, ReLU), with pad_h / pad_w
+// per axis and the slice.
+// Pool (3 x 3): max / stride 2 / no padding, max / stride 1 / pad 1, average / stride 1 / pad 1 with the number of in-image taps as the
+//   divisor -- three instances of csrc/pool_shared.h's body, which states the rule.
 // Input: x = float32(v) * 2 - 1 of a [0, 1] image, a signed image as it is; quantize: byte / 255 * 2 - 1 of the byte save_image writes
-//   (an unsigned image in its own type, a signed one from (v + 1) / 2 in fp32: selftok_lpips_input's convention).  With tap tables
+//   (px_u8 of csrc/u8_shared.h: an unsigned image in its own type, a signed one from (v + 1) / 2 in fp32).  With tap tables
 //   (i0, i1, lambda per output row and column, built on the host in fp64) a bilinear resize of the converted values, each operation
 //   rounded to fp32 on its own: top = a + lx * (b - a), bot = c + lx * (d - c) (horizontal pairs first), x = top + ly * (bot - top).
 // Spatial mean: s = +0.0f, s = s + f[p] for the pixels p in index order, then s / (float)npix, per image and channel.
@@ -24,6 +23,7 @@
 //   the same products in the same order).  No atomics; the result is a function of X alone.
 #include "common.h"
 #include "conv_f32_shared.h"
+#include "pool_shared.h"
 #include "u8_shared.h"
 #include "chunk_tree.h"
 #include "selftok_hip_ext.h"
@@ -34,7 +34,7 @@
 namespace selftok {
 namespace {
 
-using conv_f32::BM; using conv_f32::BN; using conv_f32::KT; using conv_f32::NT; using conv_f32::ConvArgs; using conv_f32::out_side;
+using conv_f32::NT; using conv_f32::ConvArgs;
 
 template <bool VEC>
 __global__ void __launch_bounds__(NT) fid_conv_kernel(ConvArgs a)
@@ -47,30 +47,7 @@ template <int MODE>
 __global__ void __launch_bounds__(NT) fid_pool_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, int C, int PH, int PW, int ldo, int co_off,
                                                       long total)
 {
-    const long i = (long)blockIdx.x * NT + threadIdx.x;
-    if (i >= total) return;
-    const int c = (int)(i % C);
-    long p = i / C;                                               // output pixel index over the batch
-    const long pixel = p;
-    const int px = (int)(p % PW); p /= PW;
-    const int py = (int)(p % PH);
-    const long n = p / PH;
-    constexpr int S = MODE == 0 ? 2 : 1, P = MODE == 0 ? 0 : 1;
-    const float* img = in + (size_t)n * H * W * C + c;
-    float m = 0.0f;
-    int count = 0;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const int iy = py * S - P + dy, ix = px * S - P + dx;
-            if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-            const float v = img[((size_t)iy * W + ix) * C];
-            if (MODE == 2) m = m + v;
-            else if (count == 0 || v > m || v != v) m = v;
-            ++count;
-        }
-    out[(size_t)pixel * ldo + co_off + c] = MODE == 2 ? m / (float)count : m;
+    pool::pool_element<3, MODE == 0 ? 2 : 1, MODE == 0 ? 0 : 1, MODE == 2>(in, out, H, W, C, PH, PW, ldo, co_off, total);
 }
 
 struct InputArgs {
@@ -82,9 +59,9 @@ struct InputArgs {
 template <bool BF>
 __device__ __forceinline__ float fid_convert(const InputArgs& a, size_t at)
 {
-    const float v = BF ? bf16_to_f32(((const unsigned short*)a.src)[at]) : ((const float*)a.src)[at];
+    const float v = load_px<BF>(a.src, at);
     if (a.quantize) {
-        const unsigned char b = a.is_signed ? to_u8_one<false>((v + 1.0f) / 2.0f) : to_u8_one<BF>(v);
+        const unsigned char b = a.is_signed ? px_u8<false>(v, true) : px_u8<BF>(v, false);        // an unsigned image in its own type: this entry's convention
         return (float)b / 255.0f * 2.0f - 1.0f;
     }
     return a.is_signed ? v : v * 2.0f - 1.0f;
@@ -200,36 +177,9 @@ extern "C" {
 int selftok_fid_conv2d_f32(const float* in, const float* packed, const float* bias, float* out, int N, int H, int W, int Cin, int Cout,
                            int KH, int KW, int stride, int pad_h, int pad_w, int ldo, int co_off, int relu, hipStream_t stream)
 {
-    if (!in || !packed || !out) { set_last_error("fid_conv2d: null pointer"); return SELFTOK_EINVAL; }
-    char msg[320];
-    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1 || pad_h < 0 || pad_h >= KH || pad_w < 0 || pad_w >= KW) {
-        snprintf(msg, sizeof msg, "fid_conv2d: need N, H, W, Cin, Cout, KH, KW, stride >= 1, 0 <= pad_h < KH and 0 <= pad_w < KW, got N %d, %d x %d, Cin %d, Cout %d, "
-                 "%d x %d, stride %d, pad %d, %d", N, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w);
-        set_last_error(msg); return SELFTOK_EINVAL;
-    }
-    if (co_off < 0 || (long)ldo < (long)co_off + Cout) {
-        snprintf(msg, sizeof msg, "fid_conv2d: the slice needs co_off >= 0 and ldo >= co_off + Cout, got ldo %d, co_off %d, Cout %d", ldo, co_off, Cout);
-        set_last_error(msg); return SELFTOK_EINVAL;
-    }
-    const int OH = out_side(H, KH, stride, pad_h), OW = out_side(W, KW, stride, pad_w);
-    if (OH < 1 || OW < 1) {
-        snprintf(msg, sizeof msg, "fid_conv2d: %d x %d input has no output pixel under a %d x %d kernel with pad %d, %d", H, W, KH, KW, pad_h, pad_w);
-        set_last_error(msg); return SELFTOK_EINVAL;
-    }
-    const long kk = (long)KH * KW;
-    if (kk >= LIM / Cin || (long)H * W >= LIM / Cin || (long)N >= LIM / ((long)H * W * Cin) || (long)OH * OW >= LIM / ldo ||
-        (long)N >= LIM / ((long)OH * OW * ldo) || ((kk * Cin + KT - 1) / KT * KT) >= LIM / ((Cout + BN - 1) / BN * BN)) {
-        snprintf(msg, sizeof msg, "fid_conv2d: input, output map and packed weight element counts must stay below 2^31, got N %d, %d x %d, Cin %d, Cout %d, %d x %d, ldo %d",
-                 N, H, W, Cin, Cout, KH, KW, ldo);
-        set_last_error(msg); return SELFTOK_EINVAL;
-    }
-    if (((uintptr_t)in & 15) != 0 || ((uintptr_t)packed & 15) != 0 || ((uintptr_t)out & 3) != 0 || ((uintptr_t)bias & 3) != 0) {
-        set_last_error("fid_conv2d: in and packed must be 16-byte aligned, out and bias 4-byte aligned"); return SELFTOK_EINVAL;
-    }
-    ConvArgs a{in, packed, bias, out, H, W, Cin, OH, OW, Cout, (Cout + BN - 1) / BN * BN, KH, KW, stride, pad_h, pad_w, KH * KW * Cin,
-               (KH * KW * Cin + KT - 1) / KT * KT, relu != 0, ldo, co_off, (long)N * OH * OW};
-    const dim3 grid((unsigned)((a.M + BM - 1) / BM), (unsigned)(a.CoutP / BN));
-    if (grid.y > 65535u) { set_last_error("fid_conv2d: Cout above 64 * 65535"); return SELFTOK_EINVAL; }
+    ConvArgs a;
+    dim3 grid;
+    if (!conv_f32::conv_plan("fid_conv2d", in, packed, bias, out, N, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w, ldo, co_off, relu, &a, &grid)) return SELFTOK_EINVAL;
     if (Cin % 4 == 0) hipLaunchKernelGGL(fid_conv_kernel<true>, grid, dim3(NT), 0, stream, a);
     else hipLaunchKernelGGL(fid_conv_kernel<false>, grid, dim3(NT), 0, stream, a);
     return check_launch("fid_conv_kernel");
@@ -237,24 +187,15 @@ int selftok_fid_conv2d_f32(const float* in, const float* packed, const float* bi
 
 int selftok_fid_pool3_f32(const float* in, float* out, int N, int H, int W, int C, int mode, int ldo, int co_off, hipStream_t stream)
 {
-    if (!in || !out) { set_last_error("fid_pool3: null pointer"); return SELFTOK_EINVAL; }
-    char msg[240];
-    const int min_side = mode == 0 ? 3 : 1;
-    if (mode < 0 || mode > 2 || N < 1 || C < 1 || H < min_side || W < min_side) {
-        snprintf(msg, sizeof msg, "fid_pool3: need mode 0 (max / 2, H, W >= 3), 1 (max, pad 1) or 2 (average, pad 1), N, C, H, W >= 1, got mode %d, N %d, %d x %d, C %d",
-                 mode, N, H, W, C);
+    if (mode < 0 || mode > 2) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "fid_pool3: need mode 0 (max / 2, H, W >= 3), 1 (max, pad 1) or 2 (average, pad 1), got mode %d", mode);
         set_last_error(msg); return SELFTOK_EINVAL;
     }
-    if (co_off < 0 || (long)ldo < (long)co_off + C) {
-        snprintf(msg, sizeof msg, "fid_pool3: the slice needs co_off >= 0 and ldo >= co_off + C, got ldo %d, co_off %d, C %d", ldo, co_off, C);
-        set_last_error(msg); return SELFTOK_EINVAL;
-    }
-    const int PH = mode == 0 ? (H - 3) / 2 + 1 : H, PW = mode == 0 ? (W - 3) / 2 + 1 : W;
-    if ((long)H * W >= LIM / C || (long)N >= LIM / ((long)H * W * C) || (long)PH * PW >= LIM / ldo || (long)N >= LIM / ((long)PH * PW * ldo)) {
-        snprintf(msg, sizeof msg, "fid_pool3: the input and the output map must stay below 2^31 elements, got N %d, %d x %d, C %d, ldo %d", N, H, W, C, ldo);
-        set_last_error(msg); return SELFTOK_EINVAL;
-    }
-    const long total = (long)N * PH * PW * C;
+    int PH, PW;
+    long total;
+    if (!(mode == 0 ? pool::check<3, 2, 0>("fid_pool3", in, out, N, H, W, C, ldo, co_off, &PH, &PW, &total)
+                    : pool::check<3, 1, 1>("fid_pool3", in, out, N, H, W, C, ldo, co_off, &PH, &PW, &total))) return SELFTOK_EINVAL;
     const dim3 grid((unsigned)((total + NT - 1) / NT));
     if (mode == 0) hipLaunchKernelGGL(fid_pool_kernel<0>, grid, dim3(NT), 0, stream, in, out, H, W, C, PH, PW, ldo, co_off, total);
     else if (mode == 1) hipLaunchKernelGGL(fid_pool_kernel<1>, grid, dim3(NT), 0, stream, in, out, H, W, C, PH, PW, ldo, co_off, total);

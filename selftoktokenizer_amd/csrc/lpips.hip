@@ -18,7 +18,8 @@
 // tile, each wave one 32 x 32 accumulator.  Per 16-deep step the im2col tile (64 rows x 16 taps, gathered with a predicate: a padding
 // tap or a row past the end is never loaded) and the weight tile (16 x 64 of the packed [KP][CoutP] image, zero-padded by the packer)
 // are fetched into registers while the previous step's MFMAs run, then stored k-major to LDS: 2 * 16 * 68 * 4 = 8704 bytes.
-// Cin % 4 == 0 gathers one float4 per thread and step; otherwise (conv1, Cin = 3) four scalar taps.
+// Cin % 4 == 0 gathers one float4 per thread and step; otherwise (conv1, Cin = 3) four scalar taps.  The tile body and the entry's host side
+// (refusals, ConvArgs, grid) are csrc/conv_f32_shared.h's; the max-pool is csrc/pool_shared.h's body, the input stage's pixel conversion csrc/u8_shared.h's.
 //
 // Distance stage: per pixel n = sqrt(sum_c f_c^2) + 1e-10 for each image, sum_c w_c (f0_c / n0 - f1_c / n1)^2, fp64 throughout and every
 // operation rounded on its own (pragma below and -ffp-contract=off).  One wave owns a pixel: lane l adds channels l, l + 64, ...
@@ -26,6 +27,7 @@
 // as (w0 + w1) + (w2 + w3); the finish adds a pair's tiles in index order and divides by the pixel count.  No atomics.
 #include "common.h"
 #include "conv_f32_shared.h"
+#include "pool_shared.h"
 #include "u8_shared.h"
 #include "selftok_hip_ext.h"
 #include <stdio.h>
@@ -35,7 +37,7 @@
 namespace selftok {
 namespace {
 
-using conv_f32::BM; using conv_f32::BN; using conv_f32::KT; using conv_f32::NT; using conv_f32::ConvArgs; using conv_f32::out_side;
+using conv_f32::BN; using conv_f32::KT; using conv_f32::NT; using conv_f32::ConvArgs;
 constexpr int MIN_SIDE = 31;
 
 // the convolution of record: conv_f32_shared.h's tile body (__builtin_amdgcn_mfma_f32_32x32x2f32), shared with csrc/fid.hip
@@ -45,26 +47,10 @@ __global__ void __launch_bounds__(NT) lpips_conv_kernel(ConvArgs a)
     conv_f32::conv_tile<VEC>(a);
 }
 
-// channels-last 3 x 3 stride 2 max-pool, floor mode, no padding: every window lies inside the image.  A NaN wins (torch's rule).
+// channels-last 3 x 3 stride 2 max-pool, floor mode, no padding: pool_shared.h's body (a NaN wins, torch's rule)
 __global__ void __launch_bounds__(NT) lpips_pool_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, int C, int PH, int PW, long total)
 {
-    const long i = (long)blockIdx.x * NT + threadIdx.x;
-    if (i >= total) return;
-    const int c = (int)(i % C);
-    long p = i / C;
-    const int px = (int)(p % PW); p /= PW;
-    const int py = (int)(p % PH);
-    const long n = p / PH;
-    const float* src = in + (((size_t)n * H + 2 * py) * W + 2 * px) * C + c;
-    float m = src[0];
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const float v = src[((size_t)dy * W + dx) * C];
-            if (v > m || v != v) m = v;
-        }
-    out[i] = m;
+    pool::pool_element<3, 2, 0, false>(in, out, H, W, C, PH, PW, C, 0, total);
 }
 
 struct InputArgs {
@@ -88,15 +74,13 @@ __global__ void __launch_bounds__(NT) lpips_input_kernel(InputArgs a)
     const size_t at = ((size_t)(is_orig ? n - a.B : n) * 3 + c) * hw + pix;
     float x;
     if (!is_orig) {
-        const float v = RB ? bf16_to_f32(((const unsigned short*)a.recon)[at]) : ((const float*)a.recon)[at];
-        if (a.quantize) x = (float)to_u8_one<RB>(v) / 255.0f * 2.0f - 1.0f;
+        const float v = load_px<RB>(a.recon, at);
+        if (a.quantize) x = (float)px_u8<RB>(v, false) / 255.0f * 2.0f - 1.0f;
         else x = v * 2.0f - 1.0f;
     } else {
-        const float v = OB ? bf16_to_f32(((const unsigned short*)a.orig)[at]) : ((const float*)a.orig)[at];
-        if (a.quantize) {
-            const float o = a.orig_signed ? (v + 1.0f) / 2.0f : v;
-            x = (float)to_u8_one<false>(o) / 255.0f * 2.0f - 1.0f;
-        } else x = a.orig_signed ? v : v * 2.0f - 1.0f;
+        const float v = load_px<OB>(a.orig, at);
+        if (a.quantize) x = (float)px_u8<false>(v, a.orig_signed) / 255.0f * 2.0f - 1.0f;
+        else x = a.orig_signed ? v : v * 2.0f - 1.0f;
     }
     const float shift = c == 0 ? -0.030f : (c == 1 ? -0.088f : -0.188f);
     const float scale = c == 0 ? 0.458f : (c == 1 ? 0.448f : 0.450f);
@@ -155,32 +139,6 @@ __global__ void __launch_bounds__(64) lpips_dist_finish_kernel(const double* __r
     out[b] = accumulate ? out[b] + v : v;
 }
 
-bool fail(const char* msg) { set_last_error(msg); return false; }
-
-bool conv_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int* OH, int* OW)
-{
-    char msg[256];
-    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0 || pad >= KH || pad >= KW) {
-        snprintf(msg, sizeof msg, "lpips_conv2d: need N, H, W, Cin, Cout, KH, KW, stride >= 1 and 0 <= pad < KH, KW, got N %d, %d x %d, Cin %d, Cout %d, %d x %d, stride %d, pad %d",
-                 N, H, W, Cin, Cout, KH, KW, stride, pad);
-        return fail(msg);
-    }
-    *OH = out_side(H, KH, stride, pad); *OW = out_side(W, KW, stride, pad);
-    if (*OH < 1 || *OW < 1) {
-        snprintf(msg, sizeof msg, "lpips_conv2d: %d x %d input has no output pixel under a %d x %d kernel with pad %d", H, W, KH, KW, pad);
-        return fail(msg);
-    }
-    const long lim = 1l << 31;
-    const long kk = (long)KH * KW;
-    if (kk >= lim / Cin || (long)H * W >= lim / Cin || (long)N >= lim / ((long)H * W * Cin) || (long)*OH * *OW >= lim / Cout ||
-        (long)N >= lim / ((long)*OH * *OW * Cout) || ((kk * Cin + KT - 1) / KT * KT) >= lim / ((Cout + BN - 1) / BN * BN)) {
-        snprintf(msg, sizeof msg, "lpips_conv2d: input, output and packed weight element counts must stay below 2^31, got N %d, %d x %d, Cin %d, Cout %d, %d x %d",
-                 N, H, W, Cin, Cout, KH, KW);
-        return fail(msg);
-    }
-    return true;
-}
-
 }  // namespace
 }  // namespace selftok
 
@@ -199,16 +157,9 @@ size_t selftok_lpips_conv2d_packed_floats(int Cin, int Cout, int KH, int KW)
 int selftok_lpips_conv2d_f32(const float* in, const float* packed, const float* bias, float* out, int N, int H, int W, int Cin, int Cout,
                              int KH, int KW, int stride, int pad, int relu, hipStream_t stream)
 {
-    if (!in || !packed || !out) { set_last_error("lpips_conv2d: null pointer"); return SELFTOK_EINVAL; }
-    int OH, OW;
-    if (!conv_plan(N, H, W, Cin, Cout, KH, KW, stride, pad, &OH, &OW)) return SELFTOK_EINVAL;
-    if (((uintptr_t)in & 15) != 0 || ((uintptr_t)packed & 15) != 0 || ((uintptr_t)out & 3) != 0 || ((uintptr_t)bias & 3) != 0) {
-        set_last_error("lpips_conv2d: in and packed must be 16-byte aligned, out and bias 4-byte aligned"); return SELFTOK_EINVAL;
-    }
-    ConvArgs a{in, packed, bias, out, H, W, Cin, OH, OW, Cout, (Cout + BN - 1) / BN * BN, KH, KW, stride, pad, pad, KH * KW * Cin,
-               (KH * KW * Cin + KT - 1) / KT * KT, relu != 0, Cout, 0, (long)N * OH * OW};
-    const dim3 grid((unsigned)((a.M + BM - 1) / BM), (unsigned)(a.CoutP / BN));
-    if (grid.y > 65535u) { set_last_error("lpips_conv2d: Cout above 64 * 65535"); return SELFTOK_EINVAL; }
+    ConvArgs a;
+    dim3 grid;
+    if (!conv_f32::conv_plan("lpips_conv2d", in, packed, bias, out, N, H, W, Cin, Cout, KH, KW, stride, pad, pad, Cout, 0, relu, &a, &grid)) return SELFTOK_EINVAL;
     if (Cin % 4 == 0) hipLaunchKernelGGL(lpips_conv_kernel<true>, grid, dim3(NT), 0, stream, a);
     else hipLaunchKernelGGL(lpips_conv_kernel<false>, grid, dim3(NT), 0, stream, a);
     return check_launch("lpips_conv_kernel");
@@ -216,17 +167,9 @@ int selftok_lpips_conv2d_f32(const float* in, const float* packed, const float* 
 
 int selftok_lpips_maxpool3s2_f32(const float* in, float* out, int N, int H, int W, int C, hipStream_t stream)
 {
-    if (!in || !out) { set_last_error("lpips_maxpool3s2: null pointer"); return SELFTOK_EINVAL; }
-    char msg[200];
-    if (N < 1 || C < 1 || H < 3 || W < 3) {
-        snprintf(msg, sizeof msg, "lpips_maxpool3s2: need N, C >= 1 and H, W >= 3 (one window), got N %d, %d x %d, C %d", N, H, W, C); set_last_error(msg); return SELFTOK_EINVAL;
-    }
-    const long lim = 1l << 31;
-    if ((long)H * W >= lim / C || (long)N >= lim / ((long)H * W * C)) {
-        snprintf(msg, sizeof msg, "lpips_maxpool3s2: N * H * W * C must stay below 2^31, got N %d, %d x %d, C %d", N, H, W, C); set_last_error(msg); return SELFTOK_EINVAL;
-    }
-    const int PH = (H - 3) / 2 + 1, PW = (W - 3) / 2 + 1;
-    const long total = (long)N * PH * PW * C;
+    int PH, PW;
+    long total;
+    if (!pool::check<3, 2, 0>("lpips_maxpool3s2", in, out, N, H, W, C, C, 0, &PH, &PW, &total)) return SELFTOK_EINVAL;
     hipLaunchKernelGGL(lpips_pool_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, stream, in, out, H, W, C, PH, PW, total);
     return check_launch("lpips_pool_kernel");
 }

@@ -299,7 +299,7 @@ class InceptionNet:
         chunk = min(self.chunk_images or max(1, CHUNK_BYTES // per_image), B)
         out = torch.empty(B, FEATURES, dtype=torch.float32, device=images.device)
         stages = []
-        arena = None if keep_stages else ops.lpips_workspace(images.device, chunk * per_image + 256 * buffers)
+        arena = None if keep_stages else ops.eval_workspace(images.device, chunk * per_image + 256 * buffers)
         for b0 in range(0, B, chunk):
             b1 = min(b0 + chunk, B)
             off = [0]

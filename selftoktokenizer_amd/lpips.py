@@ -231,7 +231,7 @@ class LpipsNet:
             _lib.check(-1, "selftok_lpips_distance_workspace_bytes")
         align = lambda v: -(-v // 256) * 256
         sizes = [align(4 * n * h * w * c) for n, h, w, c in shapes]
-        arena = ops.lpips_workspace(recon.device, sum(sizes) + align(dist_bytes))
+        arena = ops.eval_workspace(recon.device, sum(sizes) + align(dist_bytes))
         out = torch.empty(B, dtype=torch.float64, device=recon.device)
         for b0 in range(0, B, chunk):
             b1 = min(b0 + chunk, B)

@@ -59,6 +59,49 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+class _StreamWorkspace:
+    """a pool of byte workspaces: (device index, stream handle) -> tensors, largest last.  Grown on demand (never below `floor` bytes) and reused by the calls of
+    THAT stream (they are ordered); two streams never share one (their kernels could overlap); outgrown tensors stay referenced (a captured hipGraph may replay
+    on them)."""
+
+    def __init__(self, floor: int):
+        self.floor, self.held = floor, {}
+
+    def __call__(self, device, nbytes: int) -> torch.Tensor:
+        held = self.held.setdefault((device.index, int(torch.cuda.current_stream(device).cuda_stream)), [])
+        if not held or held[-1].numel() < nbytes:
+            held.append(torch.empty(max(nbytes, self.floor), dtype=torch.uint8, device=device))
+        return held[-1]
+
+
+def _ws_bytes(entry: str, *args) -> int:
+    """the size query `entry` of the library; 0 means refused: raises with the library's message"""
+    n = getattr(_lib.load(), entry)(*args)
+    if n == 0:
+        _lib.check(-1, entry)
+    return n
+
+
+def _out(what: str, out: Optional[torch.Tensor], dtype, shape, device, name: str = "out") -> torch.Tensor:
+    """`out` checked to be a contiguous `dtype` tensor of `shape`, or a fresh one when None"""
+    shape = tuple(shape)
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise _lib.SelftokHipError(f"{what}: `{name}` must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)}, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def _image_pair(what: str, recon: torch.Tensor, original: torch.Tensor):
+    """two [B, 3, H, W] tensors of one shape, bf16 or fp32 each -> both contiguous"""
+    for name, t in (("recon", recon), ("original", original)):
+        if t.dtype not in (torch.bfloat16, torch.float32):
+            raise _lib.SelftokHipError(f"{what}: `{name}` dtype {t.dtype}: expected bfloat16 or float32")
+    if recon.dim() != 4 or recon.shape[1] != 3 or tuple(original.shape) != tuple(recon.shape):
+        raise _lib.SelftokHipError(f"{what}: expected two [B, 3, H, W] tensors of one shape, got {tuple(recon.shape)} and {tuple(original.shape)}")
+    return recon.contiguous(), original.contiguous()
+
+
 def vq_pack_codebook(codebook: torch.Tensor) -> torch.Tensor:
     """[C,16] fp32 -> MFMA-fragment-ordered copy (one-time, the codebook is a constant)."""
     _need_cuda(codebook)
@@ -921,16 +964,7 @@ def ex_linear(x: torch.Tensor, weight: torch.Tensor, bias=None, *, gelu: bool = 
 
 
 LINEAR_BIAS_LAST, LINEAR_MKL_ORDER = 2, 4
-_LINEAR_WS = {}          # (device index, stream handle) -> workspace tensors of the tail split, largest last: grown on demand, reused by the calls of THAT stream (they are
-                         # ordered); two streams never share one (their tail rounds could overlap); outgrown tensors stay referenced (a captured hipGraph may replay on them)
-
-
-def _linear_ws(device, nbytes: int):
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream))
-    held = _LINEAR_WS.setdefault(key, [])
-    if not held or held[-1].numel() < nbytes:
-        held.append(torch.empty(max(nbytes, 64 << 20), dtype=torch.uint8, device=device))
-    return held[-1]
+_linear_ws = _StreamWorkspace(64 << 20)      # the tail split's workspace
 
 
 def linear_f32(x: torch.Tensor, weight: torch.Tensor, bias=None, *, mkl_order: bool = False, gelu: bool = False, res=None, res_mod: int = 0, gate=None,
@@ -1160,9 +1194,7 @@ def _image_resample(fn, entry, layout, dev_name, packed, t, size, dtype, out, t_
         return (out, {}) if return_tables else out
     lib = _lib.load()
     fa = () if filter is None else (int(filter),)
-    nbytes = getattr(lib, entry + "_workspace_bytes")(t.ctypes.data, N, S, *fa)
-    if nbytes == 0:
-        _lib.check(-1, entry + "_workspace_bytes")
+    nbytes = _ws_bytes(entry + "_workspace_bytes", t.ctypes.data, N, S, *fa)
     if t_dev is None:
         t_dev = torch.from_numpy(t).to(packed.device)
     elif t_dev.dtype != torch.int64 or t_dev.numel() != cols * N or not t_dev.is_contiguous():
@@ -1247,9 +1279,7 @@ def image_resize(packed: torch.Tensor, frames, filter, frames_dev: Optional[torc
     if N == 0:
         return packed
     lib = _lib.load()
-    nbytes = lib.selftok_img_resize_u8_workspace_bytes(t.ctypes.data, N, code)
-    if nbytes == 0:
-        _lib.check(-1, "selftok_img_resize_u8_workspace_bytes")
+    nbytes = _ws_bytes("selftok_img_resize_u8_workspace_bytes", t.ctypes.data, N, code)
     if frames_dev is None:
         frames_dev = torch.from_numpy(t).to(packed.device)
     elif frames_dev.dtype != torch.int64 or frames_dev.numel() != 6 * N or not frames_dev.is_contiguous():
@@ -1275,16 +1305,7 @@ def image_to_u8(img: torch.Tensor) -> torch.Tensor:
 
 
 # ---- device image metrics (csrc/image_metrics.hip, include/selftok_hip_ext.h) ----
-_IMG_METRICS_WS = {}     # (device index, stream handle) -> workspace tensors, largest last (the `_LINEAR_WS` rules: one stream's calls are ordered, outgrown tensors stay
-                         # referenced because a captured hipGraph may replay on them)
-
-
-def _img_metrics_ws(device, nbytes: int):
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream))
-    held = _IMG_METRICS_WS.setdefault(key, [])
-    if not held or held[-1].numel() < nbytes:
-        held.append(torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device))
-    return held[-1]
+_img_metrics_ws = _StreamWorkspace(1 << 20)
 
 
 def image_metrics(recon: torch.Tensor, original: torch.Tensor, original_signed: bool = True, quantize: bool = False) -> torch.Tensor:
@@ -1292,22 +1313,13 @@ def image_metrics(recon: torch.Tensor, original: torch.Tensor, original_signed: 
     device: {mean SSIM, MSE} per image (11 x 11 Gaussian window of sigma 1.5 = evaluate.ssim_window(), valid windows, population moments, fp64; the MSE with
     evaluate.psnr_each's operations).  `quantize`: on the bytes `image_to_u8` would write for both.  No host synchronisation; H, W >= 11."""
     _need_cuda(recon, original)
-    for name, t in (("recon", recon), ("original", original)):
-        if t.dtype not in (torch.bfloat16, torch.float32):
-            raise _lib.SelftokHipError(f"image_metrics: `{name}` dtype {t.dtype}: expected bfloat16 or float32")
-    if recon.dim() != 4 or recon.shape[1] != 3 or tuple(original.shape) != tuple(recon.shape):
-        raise _lib.SelftokHipError(f"image_metrics: expected two [B, 3, H, W] tensors of one shape, got {tuple(recon.shape)} and {tuple(original.shape)}")
+    recon, original = _image_pair("image_metrics", recon, original)
     from .evaluate import ssim_window
     win = ssim_window()
-    recon, original = recon.contiguous(), original.contiguous()
     B, _, H, W = recon.shape
-    lib = _lib.load()
-    nbytes = lib.selftok_img_metrics_workspace_bytes(B, H, W)
-    if nbytes == 0:
-        _lib.check(-1, "selftok_img_metrics_workspace_bytes")
-    ws = _img_metrics_ws(recon.device, nbytes)
+    ws = _img_metrics_ws(recon.device, _ws_bytes("selftok_img_metrics_workspace_bytes", B, H, W))
     out = torch.empty(B, 2, dtype=torch.float64, device=recon.device)
-    _lib.check(lib.selftok_img_metrics(_p(recon), int(recon.dtype == torch.bfloat16), _p(original), int(original.dtype == torch.bfloat16), int(bool(original_signed)),
+    _lib.check(_lib.load().selftok_img_metrics(_p(recon), int(recon.dtype == torch.bfloat16), _p(original), int(original.dtype == torch.bfloat16), int(bool(original_signed)),
                                        int(bool(quantize)), win.ctypes.data, _p(out), _p(ws), ws.numel(), B, H, W, _stream()), "selftok_img_metrics")
     return out
 
@@ -1340,22 +1352,13 @@ def image_ssim(recon: torch.Tensor, original: torch.Tensor, window="skimage", co
     elif cov_norm is None:
         raise ValueError("image_ssim: a window given as weights needs cov_norm (1.0: population moments)")
     _need_cuda(recon, original)
-    for name, t in (("recon", recon), ("original", original)):
-        if t.dtype not in (torch.bfloat16, torch.float32):
-            raise _lib.SelftokHipError(f"image_ssim: `{name}` dtype {t.dtype}: expected bfloat16 or float32")
-    if recon.dim() != 4 or recon.shape[1] != 3 or tuple(original.shape) != tuple(recon.shape):
-        raise _lib.SelftokHipError(f"image_ssim: expected two [B, 3, H, W] tensors of one shape, got {tuple(recon.shape)} and {tuple(original.shape)}")
+    recon, original = _image_pair("image_ssim", recon, original)
     import numpy as np
     win = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
-    recon, original = recon.contiguous(), original.contiguous()
     B, _, H, W = recon.shape
-    lib = _lib.load()
-    nbytes = lib.selftok_img_ssim_workspace_bytes(B, H, W, int(win.size))
-    if nbytes == 0:
-        _lib.check(-1, "selftok_img_ssim_workspace_bytes")
-    ws = _img_metrics_ws(recon.device, nbytes)
+    ws = _img_metrics_ws(recon.device, _ws_bytes("selftok_img_ssim_workspace_bytes", B, H, W, int(win.size)))
     out = torch.empty(B, dtype=torch.float64, device=recon.device)
-    _lib.check(lib.selftok_img_ssim(_p(recon), int(recon.dtype == torch.bfloat16), _p(original), int(original.dtype == torch.bfloat16), int(bool(original_signed)),
+    _lib.check(_lib.load().selftok_img_ssim(_p(recon), int(recon.dtype == torch.bfloat16), _p(original), int(original.dtype == torch.bfloat16), int(bool(original_signed)),
                                     int(bool(quantize)), win.ctypes.data, int(win.size), float(cov_norm), int(bool(signed_range)), _p(out), _p(ws), ws.numel(), B, H, W,
                                     _stream()), "selftok_img_ssim")
     return out
@@ -1374,13 +1377,22 @@ def lpips_pack_conv_weight(weight: torch.Tensor) -> torch.Tensor:
     if weight.dim() != 4:
         raise _lib.SelftokHipError(f"lpips_pack_conv_weight: expected [Cout, Cin, KH, KW], got {tuple(weight.shape)}")
     Cout, Cin, KH, KW = weight.shape
-    n = _lib.load().selftok_lpips_conv2d_packed_floats(Cin, Cout, KH, KW)
-    if n == 0:
-        _lib.check(-1, "selftok_lpips_conv2d_packed_floats")
+    n = _ws_bytes("selftok_lpips_conv2d_packed_floats", Cin, Cout, KH, KW)
     K, CP = KH * KW * Cin, -(-Cout // 64) * 64
     out = torch.zeros(n // CP, CP, dtype=torch.float32, device=weight.device)
     out[:K, :Cout] = weight.detach().float().permute(2, 3, 1, 0).reshape(K, Cout)
     return out
+
+
+def _conv2d(what: str, entry: str, x, packed, bias, Cout: int, KH: int, KW: int, stride: int, pad_h: int, pad_w: int):
+    """what lpips_conv2d and fid_conv2d share: the operand checks -> (x, packed, bias, the C entry `entry`, (N, OH, OW))"""
+    x, packed = _lpips_f32("x", x, 4), _lpips_f32("packed", packed, 2)
+    bias = None if bias is None else _lpips_f32("bias", bias, 1)
+    N, H, W, Cin = x.shape
+    lib = _lib.load()
+    if packed.numel() != lib.selftok_lpips_conv2d_packed_floats(Cin, Cout, KH, KW) or (bias is not None and bias.numel() != Cout):
+        raise _lib.SelftokHipError(f"{what}: packed weight of {packed.numel()} floats / bias do not belong to Cin {Cin}, Cout {Cout}, {KH} x {KW}")
+    return x, packed, bias, getattr(lib, entry), (N, (H + 2 * pad_h - KH) // stride + 1, (W + 2 * pad_w - KW) // stride + 1)
 
 
 def lpips_conv2d(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], Cout: int, KH: int, KW: int, stride: int, pad: int, relu: bool,
@@ -1389,78 +1401,50 @@ def lpips_conv2d(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
     f32-input MFMA (chain j takes the taps with k mod 16 in {2j, 2j + 1}), added as ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7)), + bias, + ReLU
     (include/selftok_hip_ext.h)."""
     _need_cuda(x, packed, bias, out)
-    x, packed = _lpips_f32("x", x, 4), _lpips_f32("packed", packed, 2)
-    bias = None if bias is None else _lpips_f32("bias", bias, 1)
-    N, H, W, Cin = x.shape
-    lib = _lib.load()
-    if packed.numel() != lib.selftok_lpips_conv2d_packed_floats(Cin, Cout, KH, KW) or (bias is not None and bias.numel() != Cout):
-        raise _lib.SelftokHipError(f"lpips_conv2d: packed weight of {packed.numel()} floats / bias do not belong to Cin {Cin}, Cout {Cout}, {KH} x {KW}")
-    OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-    if out is None:
-        out = torch.empty(N, max(OH, 0), max(OW, 0), Cout, dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (N, OH, OW, Cout) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"lpips_conv2d: `out` must be a contiguous float32 {(N, OH, OW, Cout)}, got {out.dtype} {tuple(out.shape)}")
-    _lib.check(lib.selftok_lpips_conv2d_f32(_p(x), _p(packed), _p(bias), _p(out), N, H, W, Cin, Cout, KH, KW, stride, pad, int(bool(relu)), _stream()),
-               "selftok_lpips_conv2d_f32")
+    x, packed, bias, entry, (N, OH, OW) = _conv2d("lpips_conv2d", "selftok_lpips_conv2d_f32", x, packed, bias, Cout, KH, KW, stride, pad, pad)
+    out = _out("lpips_conv2d", out, torch.float32, (N, max(OH, 0), max(OW, 0), Cout), x.device)     # no output pixel: the entry refuses
+    _lib.check(entry(_p(x), _p(packed), _p(bias), _p(out), *x.shape, Cout, KH, KW, stride, pad, int(bool(relu)), _stream()), "selftok_lpips_conv2d_f32")
+    return out
+
+
+def _lpips_maxpool(what: str, K: int, x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    _need_cuda(x, out)
+    x = _lpips_f32("x", x, 4)
+    N, H, W, C = x.shape
+    out = _out(what, out, torch.float32, (N, max((H - K) // 2 + 1, 0), max((W - K) // 2 + 1, 0), C), x.device)
+    entry = f"selftok_{what}_f32"
+    _lib.check(getattr(_lib.load(), entry)(_p(x), _p(out), N, H, W, C, _stream()), entry)
     return out
 
 
 def lpips_maxpool3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [N, H, W, C] fp32 channels-last -> [N, (H - 3) // 2 + 1, (W - 3) // 2 + 1, C]: 3 x 3 windows, stride 2, floor mode, no padding"""
-    _need_cuda(x, out)
-    x = _lpips_f32("x", x, 4)
-    N, H, W, C = x.shape
-    shape = (N, max((H - 3) // 2 + 1, 0), max((W - 3) // 2 + 1, 0), C)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"lpips_maxpool3s2: `out` must be a contiguous float32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    _lib.check(_lib.load().selftok_lpips_maxpool3s2_f32(_p(x), _p(out), N, H, W, C, _stream()), "selftok_lpips_maxpool3s2_f32")
-    return out
+    return _lpips_maxpool("lpips_maxpool3s2", 3, x, out)
 
 
 def lpips_maxpool2s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [N, H, W, C] fp32 channels-last -> [N, H // 2, W // 2, C]: 2 x 2 windows, stride 2, floor mode, no padding (VGG16's MaxPool2d(2, 2))"""
-    _need_cuda(x, out)
-    x = _lpips_f32("x", x, 4)
-    N, H, W, C = x.shape
-    shape = (N, H // 2, W // 2, C)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"lpips_maxpool2s2: `out` must be a contiguous float32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    _lib.check(_lib.load().selftok_lpips_maxpool2s2_f32(_p(x), _p(out), N, H, W, C, _stream()), "selftok_lpips_maxpool2s2_f32")
-    return out
+    return _lpips_maxpool("lpips_maxpool2s2", 2, x, out)
 
 
 def lpips_input(recon: torch.Tensor, original: torch.Tensor, original_signed: bool = True, quantize: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """recon [B, 3, H, W] in [0, 1] and original [B, 3, H, W] (bf16 or fp32 each) -> the scaling layer's output [2B, H, W, 3] fp32, recon images first"""
-    for name, t in (("recon", recon), ("original", original)):
-        if t.dtype not in (torch.bfloat16, torch.float32):
-            raise _lib.SelftokHipError(f"lpips_input: `{name}` dtype {t.dtype}: expected bfloat16 or float32")
-    if recon.dim() != 4 or recon.shape[1] != 3 or tuple(original.shape) != tuple(recon.shape):
-        raise _lib.SelftokHipError(f"lpips_input: expected two [B, 3, H, W] tensors of one shape, got {tuple(recon.shape)} and {tuple(original.shape)}")
+    recon, original = _image_pair("lpips_input", recon, original)
     _need_cuda(recon, original, out)
-    recon, original = recon.contiguous(), original.contiguous()
     B, _, H, W = recon.shape
-    if out is None:
-        out = torch.empty(2 * B, H, W, 3, dtype=torch.float32, device=recon.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (2 * B, H, W, 3) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"lpips_input: `out` must be a contiguous float32 {(2 * B, H, W, 3)}, got {out.dtype} {tuple(out.shape)}")
+    out = _out("lpips_input", out, torch.float32, (2 * B, H, W, 3), recon.device)
     _lib.check(_lib.load().selftok_lpips_input(_p(recon), int(recon.dtype == torch.bfloat16), _p(original), int(original.dtype == torch.bfloat16),
                                                int(bool(original_signed)), int(bool(quantize)), _p(out), B, H, W, _stream()), "selftok_lpips_input")
     return out
 
 
-_LPIPS_WS = {}           # (device index, stream handle) -> workspace tensors, largest last (the `_IMG_METRICS_WS` rules)
+eval_workspace = _StreamWorkspace(1 << 20)   # the evaluation arena: lpips.py and fid.py carve their stage buffers from it, the entries below their workspaces
 
 
-def lpips_workspace(device, nbytes: int) -> torch.Tensor:
-    key = (device.index, int(torch.cuda.current_stream(device).cuda_stream))
-    held = _LPIPS_WS.setdefault(key, [])
-    if not held or held[-1].numel() < nbytes:
-        held.append(torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device))
-    return held[-1]
+def _eval_ws(entry: str, args, device, workspace: Optional[torch.Tensor]) -> torch.Tensor:
+    """the workspace of an evaluation entry: its size query `entry(*args)` (a refusal raises), then the caller's tensor or the arena"""
+    nbytes = _ws_bytes(entry, *args)
+    return eval_workspace(device, nbytes) if workspace is None else workspace
 
 
 def lpips_distance(feat: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1472,18 +1456,11 @@ def lpips_distance(feat: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tens
     if N < 2 or N % 2 or w.numel() != C:
         raise _lib.SelftokHipError(f"lpips_distance: expected feat [2B, h, w, C] and w [C], got {tuple(feat.shape)} and {tuple(w.shape)}")
     B = N // 2
-    if out is None:
-        if accumulate:
-            raise _lib.SelftokHipError("lpips_distance: accumulate needs `out`")
-        out = torch.empty(B, dtype=torch.float64, device=feat.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (B,) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"lpips_distance: `out` must be a contiguous float64 [{B}], got {out.dtype} {tuple(out.shape)}")
-    lib = _lib.load()
-    nbytes = lib.selftok_lpips_distance_workspace_bytes(B, h * wd)
-    if nbytes == 0:
-        _lib.check(-1, "selftok_lpips_distance_workspace_bytes")
-    ws = lpips_workspace(feat.device, nbytes) if workspace is None else workspace
-    _lib.check(lib.selftok_lpips_distance(_p(feat), _p(w), _p(out), _p(ws), ws.numel() * ws.element_size(), B, h * wd, C, int(bool(accumulate)), _stream()),
+    if out is None and accumulate:
+        raise _lib.SelftokHipError("lpips_distance: accumulate needs `out`")
+    out = _out("lpips_distance", out, torch.float64, (B,), feat.device)
+    ws = _eval_ws("selftok_lpips_distance_workspace_bytes", (B, h * wd), feat.device, workspace)
+    _lib.check(_lib.load().selftok_lpips_distance(_p(feat), _p(w), _p(out), _p(ws), ws.numel() * ws.element_size(), B, h * wd, C, int(bool(accumulate)), _stream()),
                "selftok_lpips_distance")
     return out
 
@@ -1509,18 +1486,13 @@ def fid_conv2d(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tenso
     """lpips_conv2d's convolution (same kernel body, same packed weight) with a padding per axis, writing channels co_off .. co_off + Cout - 1 of the map
     `out` [N, OH, OW, ldo] and nothing else of it.  Returns the map."""
     _need_cuda(x, packed, bias, out)
-    x, packed = _lpips_f32("x", x, 4), _lpips_f32("packed", packed, 2)
-    bias = None if bias is None else _lpips_f32("bias", bias, 1)
-    N, H, W, Cin = x.shape
-    lib = _lib.load()
-    if packed.numel() != lib.selftok_lpips_conv2d_packed_floats(Cin, Cout, KH, KW) or (bias is not None and bias.numel() != Cout):
-        raise _lib.SelftokHipError(f"fid_conv2d: packed weight of {packed.numel()} floats / bias do not belong to Cin {Cin}, Cout {Cout}, {KH} x {KW}")
-    OH, OW = (H + 2 * pad_h - KH) // stride + 1, (W + 2 * pad_w - KW) // stride + 1
+    x, packed, bias, entry, (N, OH, OW) = _conv2d("fid_conv2d", "selftok_fid_conv2d_f32", x, packed, bias, Cout, KH, KW, stride, pad_h, pad_w)
+    _, H, W, _ = x.shape
     if H + 2 * pad_h < KH or W + 2 * pad_w < KW:                  # decided here: an empty tensor has no pointer to hand to the entry
         raise _lib.SelftokHipError(f"fid_conv2d: {H} x {W} input has no output pixel under a {KH} x {KW} kernel with pad {pad_h}, {pad_w}")
     out = _fid_slice_out("fid_conv2d", out, (N, OH, OW), Cout, co_off, x.device)
-    _lib.check(lib.selftok_fid_conv2d_f32(_p(x), _p(packed), _p(bias), _p(out), N, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w, out.shape[3], co_off,
-                                          int(bool(relu)), _stream()), "selftok_fid_conv2d_f32")
+    _lib.check(entry(_p(x), _p(packed), _p(bias), _p(out), *x.shape, Cout, KH, KW, stride, pad_h, pad_w, out.shape[3], co_off, int(bool(relu)), _stream()),
+               "selftok_fid_conv2d_f32")
     return out
 
 
@@ -1558,10 +1530,7 @@ def fid_input(images: torch.Tensor, signed: bool, quantize: bool = False, tables
             if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != 3 or not t.is_contiguous():
                 raise _lib.SelftokHipError(f"fid_input: a tap table must be a contiguous int32 [3, n], got {t.dtype} {tuple(t.shape)}")
         OH, OW = ytab.shape[1], xtab.shape[1]
-    if out is None:
-        out = torch.empty(B, OH, OW, 3, dtype=torch.float32, device=images.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, OH, OW, 3) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"fid_input: `out` must be a contiguous float32 {(B, OH, OW, 3)}, got {out.dtype} {tuple(out.shape)}")
+    out = _out("fid_input", out, torch.float32, (B, OH, OW, 3), images.device)
     _lib.check(_lib.load().selftok_fid_input(_p(images), int(images.dtype == torch.bfloat16), int(bool(signed)), int(bool(quantize)), _p(out), B, H, W, OH, OW,
                                              _p(ytab), _p(xtab), _stream()), "selftok_fid_input")
     return out
@@ -1572,10 +1541,7 @@ def fid_spatial_mean(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> tor
     _need_cuda(x, out)
     x = _lpips_f32("x", x, 4)
     N, h, w, C = x.shape
-    if out is None:
-        out = torch.empty(N, C, dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (N, C) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"fid_spatial_mean: `out` must be a contiguous float32 {(N, C)}, got {out.dtype} {tuple(out.shape)}")
+    out = _out("fid_spatial_mean", out, torch.float32, (N, C), x.device)
     _lib.check(_lib.load().selftok_fid_spatial_mean_f32(_p(x), _p(out), N, h * w, C, _stream()), "selftok_fid_spatial_mean_f32")
     return out
 
@@ -1585,17 +1551,10 @@ def fid_stats(x: torch.Tensor, mu: Optional[torch.Tensor] = None, sigma: Optiona
     _need_cuda(x, mu, sigma, workspace)
     x = _lpips_f32("x", x, 2)
     N, D = x.shape
-    lib = _lib.load()
-    nbytes = lib.selftok_fid_stats_workspace_bytes(N, D)
-    if nbytes == 0:
-        _lib.check(-1, "selftok_fid_stats_workspace_bytes")
-    for name, t, shape in (("mu", mu, (D,)), ("sigma", sigma, (D, D))):
-        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous()):
-            raise _lib.SelftokHipError(f"fid_stats: `{name}` must be a contiguous float64 {shape}, got {t.dtype} {tuple(t.shape)}")
-    mu = torch.empty(D, dtype=torch.float64, device=x.device) if mu is None else mu
-    sigma = torch.empty(D, D, dtype=torch.float64, device=x.device) if sigma is None else sigma
-    ws = lpips_workspace(x.device, nbytes) if workspace is None else workspace
-    _lib.check(lib.selftok_fid_stats(_p(x), _p(mu), _p(sigma), _p(ws), ws.numel() * ws.element_size(), N, D, _stream()), "selftok_fid_stats")
+    ws = _eval_ws("selftok_fid_stats_workspace_bytes", (N, D), x.device, workspace)
+    mu = _out("fid_stats", mu, torch.float64, (D,), x.device, "mu")
+    sigma = _out("fid_stats", sigma, torch.float64, (D, D), x.device, "sigma")
+    _lib.check(_lib.load().selftok_fid_stats(_p(x), _p(mu), _p(sigma), _p(ws), ws.numel() * ws.element_size(), N, D, _stream()), "selftok_fid_stats")
     return mu, sigma
 
 
@@ -1606,25 +1565,15 @@ def _gm_rows(name: str, t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
-def _gm_workspace(what: str, nbytes: int, device, workspace: Optional[torch.Tensor]) -> torch.Tensor:
-    if nbytes == 0:
-        _lib.check(-1, what)
-    return lpips_workspace(device, nbytes) if workspace is None else workspace
-
-
 def knn_radius(a: torch.Tensor, k: int = 3, *, split: int = 0, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """a [N, D] fp32 -> r2 [N] fp32: the k-th smallest SQUARED distance of every row to the other rows (its own index skipped), 1 <= k <= 8, N > k.
     The N x N matrix is never stored.  split: launch-shape override (0 = automatic), never visible in the result."""
     a = _gm_rows("knn_radius", a)
     _need_cuda(a, out, workspace)
     N, D = a.shape
-    lib = _lib.load()
-    ws = _gm_workspace("selftok_knn_radius_f32_workspace_bytes", lib.selftok_knn_radius_f32_workspace_bytes(N, D, int(k)), a.device, workspace)
-    if out is None:
-        out = torch.empty(N, dtype=torch.float32, device=a.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (N,) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"knn_radius: `out` must be a contiguous float32 [{N}], got {out.dtype} {tuple(out.shape)}")
-    _lib.check(lib.selftok_knn_radius_f32(_p(a), _p(out), _p(ws), ws.numel() * ws.element_size(), N, D, int(k), int(split), _stream()), "selftok_knn_radius_f32")
+    ws = _eval_ws("selftok_knn_radius_f32_workspace_bytes", (N, D, int(k)), a.device, workspace)
+    out = _out("knn_radius", out, torch.float32, (N,), a.device)
+    _lib.check(_lib.load().selftok_knn_radius_f32(_p(a), _p(out), _p(ws), ws.numel() * ws.element_size(), N, D, int(k), int(split), _stream()), "selftok_knn_radius_f32")
     return out
 
 
@@ -1638,13 +1587,9 @@ def manifold_member(x: torch.Tensor, a: torch.Tensor, r2: torch.Tensor, *, split
     if a.shape[1] != D or r2.dtype != torch.float32 or tuple(r2.shape) != (N,):
         raise _lib.SelftokHipError(f"manifold_member: expected x [M, D], a [N, D] and a float32 r2 [N], got {tuple(x.shape)}, {tuple(a.shape)}, {r2.dtype} {tuple(r2.shape)}")
     r2 = r2.contiguous()
-    lib = _lib.load()
-    ws = _gm_workspace("selftok_manifold_member_f32_workspace_bytes", lib.selftok_manifold_member_f32_workspace_bytes(M, N, D), x.device, workspace)
-    if out is None:
-        out = torch.empty(M, dtype=torch.int32, device=x.device)
-    elif out.dtype != torch.int32 or tuple(out.shape) != (M,) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"manifold_member: `out` must be a contiguous int32 [{M}], got {out.dtype} {tuple(out.shape)}")
-    _lib.check(lib.selftok_manifold_member_f32(_p(x) if M else None, _p(a), _p(r2), _p(out) if M else None, _p(ws), ws.numel() * ws.element_size(), M, N, D, int(split),
+    ws = _eval_ws("selftok_manifold_member_f32_workspace_bytes", (M, N, D), x.device, workspace)
+    out = _out("manifold_member", out, torch.int32, (M,), x.device)
+    _lib.check(_lib.load().selftok_manifold_member_f32(_p(x) if M else None, _p(a), _p(r2), _p(out) if M else None, _p(ws), ws.numel() * ws.element_size(), M, N, D, int(split),
                                                _stream()), "selftok_manifold_member_f32")
     return out
 
@@ -1660,10 +1605,9 @@ def is_colmean(logits: torch.Tensor, split_size: int, workspace: Optional[torch.
     _need_cuda(logits, workspace)
     logits = _is_logits("is_colmean", logits)
     N, C = logits.shape
-    lib = _lib.load()
-    ws = _gm_workspace("selftok_is_colmean_workspace_bytes", lib.selftok_is_colmean_workspace_bytes(N, C, int(split_size)), logits.device, workspace)
+    ws = _eval_ws("selftok_is_colmean_workspace_bytes", (N, C, int(split_size)), logits.device, workspace)
     out = torch.empty(-(-N // int(split_size)), C, dtype=torch.float64, device=logits.device)
-    _lib.check(lib.selftok_is_colmean(_p(logits), _p(out), _p(ws), ws.numel() * ws.element_size(), N, C, int(split_size), _stream()), "selftok_is_colmean")
+    _lib.check(_lib.load().selftok_is_colmean(_p(logits), _p(out), _p(ws), ws.numel() * ws.element_size(), N, C, int(split_size), _stream()), "selftok_is_colmean")
     return out
 
 
@@ -1672,12 +1616,11 @@ def is_kl_rows(logits: torch.Tensor, colmean: torch.Tensor, split_size: int, wor
     _need_cuda(logits, colmean, workspace)
     logits = _is_logits("is_kl_rows", logits)
     N, C = logits.shape
-    lib = _lib.load()
-    ws = _gm_workspace("selftok_is_kl_rows_workspace_bytes", lib.selftok_is_kl_rows_workspace_bytes(N, C, int(split_size)), logits.device, workspace)
+    ws = _eval_ws("selftok_is_kl_rows_workspace_bytes", (N, C, int(split_size)), logits.device, workspace)
     if colmean.dtype != torch.float64 or tuple(colmean.shape) != (-(-N // int(split_size)), C) or not colmean.is_contiguous():
         raise _lib.SelftokHipError(f"is_kl_rows: `colmean` must be a contiguous float64 {(-(-N // int(split_size)), C)}, got {colmean.dtype} {tuple(colmean.shape)}")
     out = torch.empty(N, dtype=torch.float64, device=logits.device)
-    _lib.check(lib.selftok_is_kl_rows(_p(logits), _p(colmean), _p(out), _p(ws), ws.numel() * ws.element_size(), N, C, int(split_size), _stream()), "selftok_is_kl_rows")
+    _lib.check(_lib.load().selftok_is_kl_rows(_p(logits), _p(colmean), _p(out), _p(ws), ws.numel() * ws.element_size(), N, C, int(split_size), _stream()), "selftok_is_kl_rows")
     return out
 
 
@@ -1698,7 +1641,7 @@ def manifold_count_nn(x: torch.Tensor, a: torch.Tensor, r2: Optional[torch.Tenso
         raise _lib.SelftokHipError("manifold_count_nn: `out_count` without r2 (no radii, no count)")
     r2 = None if r2 is None else r2.contiguous()
     lib = _lib.load()
-    ws = _gm_workspace("selftok_manifold_count_nn_f32_workspace_bytes", lib.selftok_manifold_count_nn_f32_workspace_bytes(M, N, D), x.device, workspace)
+    ws = _eval_ws("selftok_manifold_count_nn_f32_workspace_bytes", (M, N, D), x.device, workspace)
     outs = []
     for name, t, dtype, want in (("out_count", out_count, torch.int32, r2 is not None), ("out_d2", out_d2, torch.float32, True), ("out_idx", out_idx, torch.int32, True)):
         if not want:
@@ -1725,13 +1668,9 @@ def kid_sums(xs: torch.Tensor, ys: torch.Tensor, S: int, m: int, *, out: Optiona
     D = xs.shape[1]
     if tuple(xs.shape) != (S * m, D) or tuple(ys.shape) != (S * m, D) or S < 1:
         raise _lib.SelftokHipError(f"kid_sums: expected xs and ys [S * m, D] = [{S * m}, D], got {tuple(xs.shape)} and {tuple(ys.shape)}")
-    lib = _lib.load()
-    ws = _gm_workspace("selftok_kid_sums_f32_workspace_bytes", lib.selftok_kid_sums_f32_workspace_bytes(S, m, D), xs.device, workspace)
-    if out is None:
-        out = torch.empty(S, 3, dtype=torch.float64, device=xs.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (S, 3) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"kid_sums: `out` must be a contiguous float64 [{S}, 3], got {out.dtype} {tuple(out.shape)}")
-    _lib.check(lib.selftok_kid_sums_f32(_p(xs), _p(ys), _p(out), _p(ws), ws.numel() * ws.element_size(), S, m, D, _stream()), "selftok_kid_sums_f32")
+    ws = _eval_ws("selftok_kid_sums_f32_workspace_bytes", (S, m, D), xs.device, workspace)
+    out = _out("kid_sums", out, torch.float64, (S, 3), xs.device)
+    _lib.check(_lib.load().selftok_kid_sums_f32(_p(xs), _p(ys), _p(out), _p(ws), ws.numel() * ws.element_size(), S, m, D, _stream()), "selftok_kid_sums_f32")
     return out
 
 
@@ -1856,16 +1795,10 @@ def token_census(counts: torch.Tensor, out: Optional[torch.Tensor] = None, works
         raise _lib.SelftokHipError(f"token_census: `counts` must be [K, C], got {tuple(counts.shape)}")
     K, C = counts.shape
     _token_u32("token_census", "counts", counts, (K, C))
-    lib = _lib.load()
-    need = lib.selftok_token_census_workspace_bytes(K, C)
-    if need == 0:
-        _lib.check(-1, "selftok_token_census_workspace_bytes")
+    need = _ws_bytes("selftok_token_census_workspace_bytes", K, C)
     ws = torch.empty(need // 8, dtype=torch.int64, device=counts.device) if workspace is None else workspace
-    if out is None:
-        out = torch.empty(K + 1, 5, dtype=torch.float64, device=counts.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (K + 1, 5) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"token_census: `out` must be a contiguous float64 [{K + 1}, 5], got {out.dtype} {tuple(out.shape)}")
-    _lib.check(lib.selftok_token_census(_p(counts), K, C, _p(out), _p(ws), ws.numel() * ws.element_size(), _stream()), "selftok_token_census")
+    out = _out("token_census", out, torch.float64, (K + 1, 5), counts.device)
+    _lib.check(_lib.load().selftok_token_census(_p(counts), K, C, _p(out), _p(ws), ws.numel() * ws.element_size(), _stream()), "selftok_token_census")
     return out
 
 
@@ -1877,10 +1810,7 @@ def token_to_u16(ids: torch.Tensor, bad: Optional[torch.Tensor] = None, out: Opt
     if bad is None:
         bad = torch.zeros(1, dtype=torch.int32, device=ids.device)
     _token_u32("token_to_u16", "bad", bad, (1,))
-    if out is None:
-        out = torch.empty(n_rows, K, dtype=torch.uint16, device=ids.device)
-    elif out.dtype != torch.uint16 or tuple(out.shape) != (n_rows, K) or not out.is_contiguous():
-        raise _lib.SelftokHipError(f"token_to_u16: `out` must be a contiguous uint16 [{n_rows}, {K}], got {out.dtype} {tuple(out.shape)}")
+    out = _out("token_to_u16", out, torch.uint16, (n_rows, K), ids.device)
     lib = _lib.load()
     _lib.check(lib.selftok_token_to_u16(_p(ids) if n_rows else None, _TOKEN_ID_BYTES[ids.dtype], n_rows, K, rs, es, _p(out) if n_rows else None, _p(bad), _stream()),
                "selftok_token_to_u16")
@@ -1931,19 +1861,10 @@ def token_nearest(q: torch.Tensor, ref: torch.Tensor, k_range=None, exclude_self
     if ref.shape[1] != K:
         raise _lib.SelftokHipError(f"token_nearest: q and ref must have one K, got {tuple(q.shape)} and {tuple(ref.shape)}")
     k_lo, k_hi = _token_range("token_nearest", K, k_range)
-    lib = _lib.load()
-    need = lib.selftok_token_nearest_workspace_bytes(M, N)
-    if need == 0:
-        _lib.check(-1, "selftok_token_nearest_workspace_bytes")
+    need = _ws_bytes("selftok_token_nearest_workspace_bytes", M, N)
     ws = torch.empty(need // 8, dtype=torch.int64, device=q.device) if workspace is None else workspace
-    outs = []
-    for name, t in (("out_match", out_match), ("out_idx", out_idx)):
-        if t is None:
-            t = torch.empty(M, dtype=torch.int32, device=q.device)
-        elif t.dtype != torch.int32 or tuple(t.shape) != (M,) or not t.is_contiguous():
-            raise _lib.SelftokHipError(f"token_nearest: `{name}` must be a contiguous int32 [{M}], got {t.dtype} {tuple(t.shape)}")
-        outs.append(t)
+    outs = [_out("token_nearest", t, torch.int32, (M,), q.device, name) for name, t in (("out_match", out_match), ("out_idx", out_idx))]
     if M:
-        _lib.check(lib.selftok_token_nearest(_p(q), M, _p(ref) if N else None, N, K, k_lo, k_hi, int(exclude_self), int(split), _p(outs[0]), _p(outs[1]), _p(ws),
+        _lib.check(_lib.load().selftok_token_nearest(_p(q), M, _p(ref) if N else None, N, K, k_lo, k_hi, int(exclude_self), int(split), _p(outs[0]), _p(outs[1]), _p(ws),
                                              ws.numel() * ws.element_size(), _stream()), "selftok_token_nearest")
     return outs[0], outs[1]

@@ -133,9 +133,22 @@ def pool_np(x, mode):
         return (acc / cnt.astype(f32)).astype(f32) if mode == "avg_s1p1" else acc
 
 
-@pytest.mark.parametrize("mode", ["max_s2", "max_s1p1", "avg_s1p1"])
-@pytest.mark.parametrize("shape", [(1, 64, 7, 7), (3, 32, 3, 3), (2, 16, 1, 1), (2, 24, 1, 2), (1, 8, 9, 11), (3, 192, 4, 5)], ids=str)
+POOL_CASES = [pytest.param(mode, shape, id=f"{shape}-{mode}") for mode in ("max_s2", "max_s1p1", "avg_s1p1")
+              for shape in [(1, 64, 7, 7), (3, 32, 3, 3), (2, 16, 1, 1), (2, 24, 1, 2), (1, 8, 9, 11), (3, 192, 4, 5)]]
+POOL_CASES.append(pytest.param("lpips_maxpool3s2", [(1, 3, 3, 1), (2, 7, 8, 5), (1, 9, 11, 24)], id="lpips_maxpool3s2-is-max_s2"))      # [N, H, W, C]
+
+
+@pytest.mark.parametrize("mode,shape", POOL_CASES)
 def test_pools_equal_the_stated_order(mode, shape):
+    if mode == "lpips_maxpool3s2":                                 # the LPIPS 3 x 3 / 2 pool and mode max_s2 are one body (csrc/pool_shared.h): the same bits
+        for s in shape:
+            x = synth.hash_uniform(synth.name_seed(f"pool_eq_{s}"), s, -1.0, -0.01).numpy()       # negative, so the planted -0.0 is the largest value of its windows
+            x[0, s[1] // 2, s[2] // 2, 0] = np.nan
+            x[-1, 0, 0, -1] = -0.0
+            a, b = ops.lpips_maxpool3s2(dev(x)).cpu().numpy(), ops.fid_pool3(dev(x), "max_s2").cpu().numpy()
+            assert a.shape == (s[0], (s[1] - 3) // 2 + 1, (s[2] - 3) // 2 + 1, s[3]) and same(a, b), s
+            assert np.isnan(a).sum() >= 1 and ((bits(a) == 0x80000000).sum() >= 1 or a.size == 1), s      # both plants are seen (3 x 3 x 1: the NaN owns the one output)
+        return
     N, C, H, W = shape
     if mode == "max_s2" and min(H, W) < 3:
         with pytest.raises(_lib.SelftokHipError, match="H, W >= 3"):
