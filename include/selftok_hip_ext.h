@@ -408,6 +408,42 @@ size_t selftok_token_nearest_workspace_bytes(int M, int N);
 int selftok_token_nearest(const unsigned short* q, int M, const unsigned short* ref, int N, int K, int k_lo, int k_hi, int exclude_self, int split, int* best_match,
                           int* best_idx, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* ---- token sampler: AR logits over a window of C codes -> one code id per row (csrc/token_sample.hip) -------------------------------
+ * Classifier-free guidance on the logits, temperature, top-k, top-p and one counter-based draw, reproducible bit for bit in numpy float32 /
+ * uint64 (tests/token_sample_cases.py is that restatement): no library exponential, no floating-point sum whose order matters, no fused
+ * multiply-add.  Stateless and capturable, no workspace, no synchronisation; every refusal is decided on the host before the launch
+ * (SELFTOK_EINVAL with a message) and leaves the outputs untouched.  A row's outputs depend on that row's inputs alone.
+ *
+ * Inputs.  Row b of `logits` (and of `uncond_logits`, the same layout, or null) holds its window at elements b * row_stride + offset ..
+ *   + C - 1; dtype 0 = fp32, 1 = bf16 (widened exactly).  1 <= C <= 65536, offset + C <= row_stride.  The pointers are aligned to four codes
+ *   (16 bytes fp32, 8 bytes bf16), offset and (for B > 1) row_stride are multiples of 4.  ctr: uint32 [B, 2]; pos: int32 [B] or null.
+ * 1. l = lu + s * (lc - lu), s = cfg_scale: difference, product, sum, each rounded to fp32; skipped when uncond_logits is null.  Then
+ *    l = l * inv_T, inv_T = 1.0f / temperature computed once on the host.  temperature == 0 is GREEDY: inv_T = 1, the kept set is the first
+ *    code of the order of (3), no random number is consumed.
+ * 2. A row whose l holds a NaN or +inf, or nothing above -inf, is BAD: id -1, n_kept 0, masses 0, logprob NaN, bad[0] += 1, nothing else
+ *    written.  (Guidance turns -inf in both inputs into NaN: mask codes with a large finite negative, or after the guidance.)  A row whose
+ *    pos[b] lies outside [0, id_cols) is bad too, and its id is not written at all.
+ * 3. Total order: l descending, index ascending on equal bits (a monotone uint32 key of l; -0.0 counts as +0.0).  Both filters keep a
+ *    PREFIX of this order: ties are cut by index, never by chance.
+ * 4. Integer mass, m the row maximum, d = l - m <= 0 in fp32: n = rint(d * 1.4426950408889634f); r = (d - n * 0.693145751953125f) -
+ *    n * 1.428606765330187045e-06f; p = ((((((c6 r + c5) r + c4) r + c3) r + 1/2) r + 1) r + 1), c6 .. c3 = 1/720, 1/120, 1/24, 1/6 rounded
+ *    to fp32, separate fp32 multiplies and adds; w = p * 2^(n + 32) (exact); q = (uint64) w (truncated); q = 0 for l = -inf or d < -24.  The
+ *    maximum gets exactly 2^32; the relative error of w against exp is below 2^-21.  A code more than about 22.2 below the maximum has
+ *    mass 0 and is never drawn.  Sums of up to 65536 masses stay below 2^49.
+ * 5. top_k keeps the first min(k, C) codes of the order (k <= 0: off); their mass is Q_k.
+ * 6. top_p, 0 < P < 1: T = (uint64) ceil((double) P * (double) Q_k); the kept set is the shortest prefix of the top-k prefix whose mass is
+ *    >= T (at least one code).  P >= 1 or P <= 0: off.  Its mass is Q_kept.
+ * 7. Draw: Philox4x32-10, key (seed_lo, seed_hi), counter (ctr[b][0], ctr[b][1], 0, 0); u = out[0] | out[1] << 32; r = mulhi64(u, Q_kept);
+ *    the chosen code is the first kept code IN ASCENDING INDEX whose running mass exceeds r.
+ * 8. Outputs: the id (0-based inside the window) as int32 / int64 (id_bytes 4 / 8) at element b * id_row_stride + (pos ? pos[b] : 0) of
+ *    ids_out; n_kept[b] int32; mass[b] = (Q_total, Q_kept, q_id) uint64, Q_total the mass of the whole window; logprob[b] fp32 =
+ *    ((double) l_id - (double) m) - log((double) Q_total * 2^-32), fp64 rounded once: the log-probability of the chosen code under the
+ *    temperature-scaled UNFILTERED distribution.
+ * B == 0 returns 0 without a launch. */
+int selftok_sample_token(const void* logits, const void* uncond_logits, int dtype, int B, int C, long row_stride, long offset, float cfg_scale, float temperature,
+                         int top_k, float top_p, unsigned seed_lo, unsigned seed_hi, const unsigned* ctr, const int* pos, void* ids_out, int id_bytes,
+                         long id_row_stride, int id_cols, int* n_kept, unsigned long long* mass, float* logprob, unsigned* bad, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

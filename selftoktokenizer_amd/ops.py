@@ -1868,3 +1868,63 @@ def token_nearest(q: torch.Tensor, ref: torch.Tensor, k_range=None, exclude_self
         _lib.check(_lib.load().selftok_token_nearest(_p(q), M, _p(ref) if N else None, N, K, k_lo, k_hi, int(exclude_self), int(split), _p(outs[0]), _p(outs[1]), _p(ws),
                                              ws.numel() * ws.element_size(), _stream()), "selftok_token_nearest")
     return outs[0], outs[1]
+
+
+# ----------------------------------------------------------------------------------------------
+# token sampler (csrc/token_sample.hip): AR logits over a window of codes -> one code id per row
+# ----------------------------------------------------------------------------------------------
+_SAMPLE_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
+
+
+def token_sample(logits: torch.Tensor, ctr: torch.Tensor, ids_out: torch.Tensor, *, uncond_logits: Optional[torch.Tensor] = None, C: Optional[int] = None,
+                 offset: int = 0, cfg_scale: float = 1.0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                 pos: Optional[torch.Tensor] = None, col: int = 0, n_kept: Optional[torch.Tensor] = None, mass: Optional[torch.Tensor] = None,
+                 logprob: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None):
+    """One code id per row of `logits` [B, V] (fp32 or bf16, row stride a multiple of 4 codes) over the window [offset, offset + C) (default: the rest of the
+    row): guidance `lu + cfg_scale * (lc - lu)` when `uncond_logits` (same shape, dtype and strides) is given, temperature (0 = greedy), top-k (<= 0 off),
+    top-p (outside (0, 1) off) and one Philox4x32-10 draw per row with key `seed` (64 bits) and counter ctr[b] (32-bit [B, 2]) -- include/selftok_hip_ext.h
+    states the arithmetic, which numpy reproduces bit for bit.  The id (0-based inside the window) of row b is written to ids_out[b, pos[b]] (`pos` int32 [B]) or
+    ids_out[b, col]; ids_out is int32 or int64 [B, K] with unit column stride.  -> (n_kept int32 [B], mass int64 [B, 3] holding the uint64 (Q_total, Q_kept,
+    q_id), logprob fp32 [B], bad 32-bit [1], accumulating).  A bad row (NaN / +inf / all -inf, or pos outside [0, K)) gets id -1, n_kept 0, masses 0, logprob
+    NaN and adds 1 to bad.  No synchronisation, nothing read back."""
+    _need_cuda(logits, uncond_logits, ctr, ids_out, pos, n_kept, mass, logprob, bad)
+    what = "token_sample"
+    if logits.dtype not in _SAMPLE_DTYPES or logits.dim() != 2:
+        raise _lib.SelftokHipError(f"{what}: `logits` must be fp32 or bf16 [B, V], got {logits.dtype} {tuple(logits.shape)}")
+    B, V = logits.shape
+    if C is None:
+        C = V - int(offset)
+    C, offset = int(C), int(offset)
+    if offset < 0 or C < 1 or offset + C > V:
+        raise _lib.SelftokHipError(f"{what}: the window [{offset}, {offset} + {C}) does not lie inside a row of {V} codes")
+    if V and logits.stride(1) != 1:
+        raise _lib.SelftokHipError(f"{what}: `logits` rows must have unit element stride, got strides {logits.stride()}")
+    rs = logits.stride(0) if B > 1 else max(V, logits.stride(0))
+    if uncond_logits is not None and (uncond_logits.dtype != logits.dtype or uncond_logits.shape != logits.shape or (B > 1 and uncond_logits.stride() != logits.stride())
+                                      or uncond_logits.stride(1) != 1):
+        raise _lib.SelftokHipError(f"{what}: `uncond_logits` must have the dtype, shape and strides of `logits`")
+    if ctr.dtype not in (torch.int32, torch.uint32) or tuple(ctr.shape) != (B, 2) or not ctr.is_contiguous():
+        raise _lib.SelftokHipError(f"{what}: `ctr` must be a contiguous 32-bit integer tensor [{B}, 2], got {ctr.dtype} {tuple(ctr.shape)}")
+    if ids_out.dtype not in (torch.int32, torch.int64) or ids_out.dim() != 2 or ids_out.shape[0] != B or ids_out.shape[1] < 1 or ids_out.stride(1) != 1 or \
+            (B > 1 and ids_out.stride(0) < ids_out.shape[1]):
+        raise _lib.SelftokHipError(f"{what}: `ids_out` must be int32 or int64 [{B}, K] with unit column stride, got {ids_out.dtype} {tuple(ids_out.shape)}")
+    K = ids_out.shape[1]
+    if pos is not None:
+        if pos.dtype != torch.int32 or tuple(pos.shape) != (B,) or not pos.is_contiguous():
+            raise _lib.SelftokHipError(f"{what}: `pos` must be a contiguous int32 tensor [{B}], got {pos.dtype} {tuple(pos.shape)}")
+    elif not 0 <= int(col) < K:
+        raise _lib.SelftokHipError(f"{what}: col {col} outside [0, {K})")
+    dev = logits.device
+    n_kept = _out(what, n_kept, torch.int32, (B,), dev, "n_kept")
+    mass = _out(what, mass, torch.int64, (B, 3), dev, "mass")
+    logprob = _out(what, logprob, torch.float32, (B,), dev, "logprob")
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    _token_u32(what, "bad", bad, (1,))
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ids_ptr = _p(ids_out) + (0 if pos is not None else int(col) * ids_out.element_size())
+    _lib.check(_lib.load().selftok_sample_token(_p(logits), _p(uncond_logits), _SAMPLE_DTYPES[logits.dtype], B, C, rs, offset, float(cfg_scale), float(temperature),
+                                                int(top_k), float(top_p), seed & 0xFFFFFFFF, seed >> 32, _p(ctr), _p(pos), ids_ptr, ids_out.element_size(),
+                                                ids_out.stride(0) if B > 1 else K, K if pos is not None else 1, _p(n_kept), _p(mass), _p(logprob), _p(bad), _stream()),
+               "selftok_sample_token")
+    return n_kept, mass, logprob, bad

@@ -1,0 +1,129 @@
+"""The step that produces the ids: AR logits -> code ids on the device, bit-reproducible (csrc/token_sample.hip, `ops.token_sample`).
+
+An AR image model emits one row of logits per sample and step; `TokenSampler` turns them into the `[B, K]` id matrix that
+`SelftokPipeline.decoding(ids, ar_partial=m)` and `DecodeStream.submit(ids, ar_partial=m)` take.  AR step s of a sample lands at tokenizer
+position K - 1 - s (tokens.py: the model emits position K - 1 first).  The draw of a sample at a step is a function of (seed, ticket, step)
+and that sample's logits alone: the same request gives the same ids alone or in any batch, in any row, run to run, and after a
+`state()` / `load_state()` round trip.  Nothing is read back and nothing synchronises: the counters live and advance on the device.
+
+    sampler = TokenSampler(K=512, temperature=1.0, top_k=50, top_p=0.9, cfg_scale=3.0, seed=1234)
+    sampler.begin(B)                                   # tickets 0 .. B - 1; pass `tickets=` to name requests yourself
+    for s in range(K):
+        sampler.step(cond_logits, uncond_logits)       # [B, V] fp32 or bf16, the codes at [offset, offset + C)
+        if s % 64 == 63:
+            ids, m = sampler.partial()
+            preview = pipe.decoding(ids, ar_partial=m)
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops as _ops
+
+
+class TokenSampler:
+    """K: tokens per image.  C / offset: the window of image codes inside a logits row.  temperature 0 is greedy; top_k <= 0 and top_p outside (0, 1) are
+    off; cfg_scale None means no guidance (`step` then refuses unconditional logits, and demands them otherwise).  seed: 64 bits, the Philox key."""
+
+    def __init__(self, K: int, C: int = 32768, offset: int = 0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, cfg_scale: Optional[float] = None,
+                 seed: int = 0, *, id_dtype=torch.int64, ops=None):
+        if K < 1 or not 1 <= C <= 65536 or offset < 0 or offset % 4:
+            raise ValueError(f"need K >= 1, 1 <= C <= 65536 and an offset >= 0 that is a multiple of 4, got K {K}, C {C}, offset {offset}")
+        if not (temperature >= 0.0) or temperature == float("inf") or top_p != top_p:
+            raise ValueError(f"need a finite temperature >= 0 and a top_p that is a number, got {temperature}, {top_p}")
+        if id_dtype not in (torch.int32, torch.int64):
+            raise ValueError("id_dtype must be torch.int32 or torch.int64")
+        self.K, self.C, self.offset = int(K), int(C), int(offset)
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        self.cfg_scale = None if cfg_scale is None else float(cfg_scale)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.id_dtype = id_dtype
+        self._ops = _ops if ops is None else ops
+        self.B = None
+
+    # ---- a batch of requests ----
+    def begin(self, B: int, tickets=None, steps=None, device="cuda"):
+        """allocate ids / logprob / n_kept [B, K] (ids and n_kept zeroed, logprob NaN) and the counters (ticket, step) [B, 2].  tickets: one 32-bit number per
+        row, default 0 .. B - 1 -- the identity of a request: its draws do not depend on the row it sits in.  steps: the AR step each row starts at, default 0;
+        rows at different steps share every call through a per-row write position."""
+        B = int(B)
+        tickets = np.arange(B, dtype=np.int64) if tickets is None else np.asarray(tickets, dtype=np.int64).reshape(-1)
+        steps = np.zeros(B, dtype=np.int64) if steps is None else np.asarray(steps, dtype=np.int64).reshape(-1)
+        if tickets.shape != (B,) or steps.shape != (B,) or (B and (tickets.min() < 0 or tickets.max() > 0xFFFFFFFF or steps.min() < 0 or steps.max() > self.K)):
+            raise ValueError(f"need {B} tickets in [0, 2^32) and {B} steps in [0, K]")
+        self.B = B
+        self._steps = steps.copy()                                  # host mirror: the device never has to be asked
+        ctr = np.stack([tickets, steps], axis=1).astype(np.uint32).view(np.int32)
+        self.ctr = torch.from_numpy(ctr.copy()).to(device)
+        self.ids = torch.zeros(B, self.K, dtype=self.id_dtype, device=device)
+        self.logprob = torch.full((B, self.K), float("nan"), dtype=torch.float32, device=device)
+        self.n_kept = torch.zeros(B, self.K, dtype=torch.int32, device=device)
+        self.bad = torch.zeros(1, dtype=torch.int32, device=device)
+        self._row_lp = torch.empty(B, dtype=torch.float32, device=device)
+        self._row_nk = torch.empty(B, dtype=torch.int32, device=device)
+        self._row_mass = torch.empty(B, 3, dtype=torch.int64, device=device)
+        return self
+
+    def _uniform(self) -> bool:
+        return self.B == 0 or bool((self._steps == self._steps[0]).all())
+
+    def step(self, logits: torch.Tensor, uncond_logits: Optional[torch.Tensor] = None):
+        """sample the next AR step of every row: row b's id goes to tokenizer position K - 1 - step_b, its log-probability and kept count beside it, and the
+        counters advance on the device.  Reads nothing back."""
+        if self.B is None:
+            raise RuntimeError("TokenSampler.step before begin")
+        if (uncond_logits is None) != (self.cfg_scale is None):
+            raise ValueError("unconditional logits go with a cfg_scale: pass both or neither")
+        if self.B and int(self._steps.max()) >= self.K:
+            raise RuntimeError(f"a row already holds its K = {self.K} tokens")
+        kw = dict(uncond_logits=uncond_logits, C=self.C, offset=self.offset, cfg_scale=1.0 if self.cfg_scale is None else self.cfg_scale,
+                  temperature=self.temperature, top_k=self.top_k, top_p=self.top_p, seed=self.seed, n_kept=self._row_nk, mass=self._row_mass,
+                  logprob=self._row_lp, bad=self.bad)
+        if self._uniform():
+            col = self.K - 1 - int(self._steps[0]) if self.B else 0
+            self._ops.token_sample(logits, self.ctr, self.ids, col=col, **kw)
+            self.logprob[:, col].copy_(self._row_lp)
+            self.n_kept[:, col].copy_(self._row_nk)
+        else:
+            pos = (self.K - 1) - self.ctr[:, 1]                     # int32, on the device
+            self._ops.token_sample(logits, self.ctr, self.ids, pos=pos, **kw)
+            p64 = pos.to(torch.int64).unsqueeze(1)
+            self.logprob.scatter_(1, p64, self._row_lp.unsqueeze(1))
+            self.n_kept.scatter_(1, p64, self._row_nk.unsqueeze(1))
+        self.ctr[:, 1] += 1
+        self._steps += 1
+        return self
+
+    def partial(self):
+        """(ids [B, K], m): the arguments of `SelftokPipeline.decoding(ids, ar_partial=m)` and `DecodeStream.submit(ids[b], ar_partial=m_b)`; m is an int when
+        every row is at the same step, else one value per row"""
+        if self.B is None:
+            raise RuntimeError("TokenSampler.partial before begin")
+        return self.ids, (int(self._steps[0]) if self.B and self._uniform() else self._steps.copy())
+
+    # ---- resumable requests ----
+    def state(self) -> dict:
+        """everything a later `load_state` needs to continue bit for bit (one device -> host copy: not for the inner loop)"""
+        if self.B is None:
+            raise RuntimeError("TokenSampler.state before begin")
+        return {"K": self.K, "C": self.C, "offset": self.offset, "temperature": self.temperature, "top_k": self.top_k, "top_p": self.top_p,
+                "cfg_scale": self.cfg_scale, "seed": self.seed, "id_dtype": str(self.id_dtype).replace("torch.", ""),
+                "ctr": self.ctr.cpu().numpy().view(np.uint32).copy(), "steps": self._steps.copy(), "ids": self.ids.cpu().numpy().copy(),
+                "logprob": self.logprob.cpu().numpy().copy(), "n_kept": self.n_kept.cpu().numpy().copy(), "bad": int(self.bad.cpu()[0])}
+
+    def load_state(self, st: dict, device="cuda"):
+        for name in ("K", "C", "offset", "temperature", "top_k", "top_p", "cfg_scale", "seed"):
+            if st[name] != getattr(self, name):
+                raise ValueError(f"state was saved with {name} = {st[name]!r}, this sampler has {getattr(self, name)!r}")
+        ctr = np.asarray(st["ctr"], dtype=np.uint32)
+        self.begin(ctr.shape[0], tickets=ctr[:, 0], steps=np.asarray(st["steps"]), device=device)
+        if not np.array_equal(ctr[:, 1].astype(np.int64), self._steps):
+            raise ValueError("state: the counters' step words and `steps` differ")
+        self.ids.copy_(torch.from_numpy(np.asarray(st["ids"])).to(self.id_dtype))
+        self.logprob.copy_(torch.from_numpy(np.asarray(st["logprob"], dtype=np.float32)))
+        self.n_kept.copy_(torch.from_numpy(np.asarray(st["n_kept"], dtype=np.int32)))
+        self.bad.fill_(int(st["bad"]))
+        return self
