@@ -444,6 +444,35 @@ int selftok_sample_token(const void* logits, const void* uncond_logits, int dtyp
                          int top_k, float top_p, unsigned seed_lo, unsigned seed_hi, const unsigned* ctr, const int* pos, void* ids_out, int id_bytes,
                          long id_row_stride, int id_cols, int* n_kept, unsigned long long* mass, float* logprob, unsigned* bad, hipStream_t stream);
 
+/* ---- token scorer: AR logits over a window of C codes and a KNOWN id per row -> log-probability, rank, first code, entropy (csrc/token_score.hip) ----
+ * The teacher-forced side of the sampler above, on the sampler's arithmetic: steps 1 - 4 of its text hold here word for word (guidance as difference,
+ * product, sum; l * inv_T; the key and the total order "l descending, index ascending", -0.0 = +0.0; the integer mass q with the same constants, q = 0 for
+ * d < -24, exactly 2^32 at the maximum), so that the two kernels can be held to each other by equality (tests/token_score_cases.py restates the rest in
+ * numpy).  Stateless and capturable, no workspace, no synchronisation; every refusal is decided on the host before the launch (SELFTOK_EINVAL with a
+ * message) and leaves the outputs untouched.  A row's outputs depend on that row's inputs alone.
+ *
+ * Inputs.  logits, uncond_logits, dtype, C, row_stride, offset, cfg_scale: the sampler's layout, alignment and window rules, R rows (R < 2^31, 64-bit
+ *   element offsets).  temperature must be finite and > 0: a greedy distribution has no log-probabilities.  The target of row r is the int32 / int64
+ *   (id_bytes 4 / 8) at element (r / S) * id_seq_stride + (r % S) * id_step_stride of `ids`, S = rows_per_seq >= 1, strides in ELEMENTS,
+ *   id_step_stride possibly negative (the caller passes the base pointer already offset, and owns every element so addressed): rows of [B, S, V]
+ *   logits in AR order score against [B, K] ids in tokenizer order without a flipped copy.  A target is 0-based inside the window.
+ * Outputs, dense [R]:
+ *   logprob fp32 = ((double) l_t - (double) m) - log((double) Q_total * 2^-32), rounded once: the sampler's formula.  A target more than 24 below the
+ *     maximum has q_t = 0 and still a finite logprob; a target at -inf gets -inf.
+ *   mass uint64 [R, 2] = (Q_total, q_t).
+ *   rank int32 = the number of codes strictly ahead of the target in the total order (0: the target is what the sampler's greedy mode picks).
+ *   top_id int32 = the first code of the order.
+ *   entropy fp32, of the distribution the integer masses define: h_i = (uint64) trunc((double) q_i * (double) (-d_i) * 65536.0) for q_i > 0, else 0
+ *     (two fp64 products, left to right); S_h = sum h_i, an integer sum (h_i < 2^47 since x e^-x <= 0.368, so S_h < 2^63 at C = 65536);
+ *     H = log((double) Q_total * 2^-32) + (double) S_h / (65536.0 * (double) Q_total), fp64 rounded once.
+ * Row kinds.  BAD: a NaN or +inf in l, nothing above -inf, or a target >= C: logprob NaN, rank -1, top_id -1, masses 0, entropy NaN, bad[0] += 1.
+ *   IGNORED (the padding of a partial sequence): a target < 0 on a row that is not bad: logprob 0.0, rank -1, q_t 0; Q_total, top_id and entropy
+ *   are written as for any row; ignored[0] += 1.  bad and ignored accumulate: the caller zeroes them.
+ * R == 0 returns 0 without a launch. */
+int selftok_score_tokens(const void* logits, const void* uncond_logits, int dtype, int R, int C, long row_stride, long offset, float cfg_scale, float temperature,
+                         const void* ids, int id_bytes, int rows_per_seq, long id_seq_stride, long id_step_stride, float* logprob, unsigned long long* mass,
+                         int* rank, int* top_id, float* entropy, unsigned* bad, unsigned* ignored, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1928,3 +1928,84 @@ def token_sample(logits: torch.Tensor, ctr: torch.Tensor, ids_out: torch.Tensor,
                                                 ids_out.stride(0) if B > 1 else K, K if pos is not None else 1, _p(n_kept), _p(mass), _p(logprob), _p(bad), _stream()),
                "selftok_sample_token")
     return n_kept, mass, logprob, bad
+
+
+# ----------------------------------------------------------------------------------------------
+# token scorer (csrc/token_score.hip): AR logits and KNOWN ids -> log-probability, rank, first code, entropy per row
+# ----------------------------------------------------------------------------------------------
+def token_score(logits: torch.Tensor, ids: torch.Tensor, *, uncond_logits: Optional[torch.Tensor] = None, C: Optional[int] = None, offset: int = 0,
+                cfg_scale: float = 1.0, temperature: float = 1.0, rows_per_seq: Optional[int] = None, reverse_steps: bool = False,
+                logprob: Optional[torch.Tensor] = None, mass: Optional[torch.Tensor] = None, rank: Optional[torch.Tensor] = None,
+                top_id: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None,
+                ignored: Optional[torch.Tensor] = None):
+    """Teacher-forced scores of known ids: `logits` [R, V] or [B, S, V] (fp32 or bf16, unit code stride, row stride a multiple of 4 codes; [B, S, V] must
+    flatten to rows without a copy) over the window [offset, offset + C) (default: the rest of the row), with the sampler's guidance (`uncond_logits`,
+    `cfg_scale`) and `temperature` > 0 -- include/selftok_hip_ext.h states the arithmetic, the sampler's own.  `ids`: int32 or int64, [R] or [B, S] (R = B * S),
+    ANY strided view (a column range of a wider [B, K] matrix, every other column, an expanded row): the two id strides are taken from it and nothing is
+    copied.  `reverse_steps` reads the steps of a sequence backwards -- row (b, s) scores ids[b, S - 1 - s] -- which is how AR-ordered logits meet
+    tokenizer-ordered ids (torch has no negative strides; the kernel has).  `rows_per_seq`, if given, must be the S so derived.  A target is 0-based inside
+    the window; a target < 0 is IGNORED (padding), a target >= C makes the row BAD, as does a NaN / +inf / all -inf row.
+    -> (logprob fp32, mass int64 [..., 2] holding the uint64 (Q_total, q_t), rank int32, top_id int32, entropy fp32, bad 32-bit [1], ignored 32-bit [1]), the
+    row outputs shaped [R] or [B, S]; bad and ignored ACCUMULATE.  Preallocated outputs are taken as given.  No synchronisation, nothing read back."""
+    _need_cuda(logits, uncond_logits, ids, logprob, mass, rank, top_id, entropy, bad, ignored)
+    what = "token_score"
+    if logits.dtype not in _SAMPLE_DTYPES or logits.dim() not in (2, 3):
+        raise _lib.SelftokHipError(f"{what}: `logits` must be fp32 or bf16 [R, V] or [B, S, V], got {logits.dtype} {tuple(logits.shape)}")
+    V = logits.shape[-1]
+    rows_shape = tuple(logits.shape[:-1])
+    R = 1
+    for n in rows_shape:
+        R *= int(n)
+    if R >= 1 << 31:
+        raise _lib.SelftokHipError(f"{what}: {R} rows: need fewer than 2^31")
+    if C is None:
+        C = V - int(offset)
+    C, offset = int(C), int(offset)
+    if offset < 0 or C < 1 or offset + C > V:
+        raise _lib.SelftokHipError(f"{what}: the window [{offset}, {offset} + {C}) does not lie inside a row of {V} codes")
+    if V and logits.stride(-1) != 1:
+        raise _lib.SelftokHipError(f"{what}: `logits` rows must have unit element stride, got strides {logits.stride()}")
+    if logits.dim() == 3 and R > 1 and logits.shape[0] > 1 and logits.shape[1] > 1 and logits.stride(0) != logits.shape[1] * logits.stride(1):
+        raise _lib.SelftokHipError(f"{what}: [B, S, V] `logits` must flatten to rows without a copy (stride(0) == S * stride(1)), got strides {logits.stride()}")
+    if logits.dim() == 2 or logits.shape[1] > 1:
+        rs = logits.stride(-2)
+    else:
+        rs = logits.stride(0)
+    if R <= 1:
+        rs = max(V, rs)
+    if uncond_logits is not None and (uncond_logits.dtype != logits.dtype or uncond_logits.shape != logits.shape or (R > 1 and uncond_logits.stride() != logits.stride())
+                                      or uncond_logits.stride(-1) != 1):
+        raise _lib.SelftokHipError(f"{what}: `uncond_logits` must have the dtype, shape and strides of `logits`")
+    if ids.dtype not in (torch.int32, torch.int64) or ids.dim() not in (1, 2) or ids.numel() != R or (logits.dim() == 3 and ids.dim() == 2 and tuple(ids.shape) != rows_shape):
+        raise _lib.SelftokHipError(f"{what}: `ids` must be int32 or int64, [R] or [B, S] with one id per row of `logits` ({R}), got {ids.dtype} {tuple(ids.shape)}")
+    if ids.dim() == 2:
+        S, seq_stride, step_stride = int(ids.shape[1]), int(ids.stride(0)), int(ids.stride(1))
+    else:                                                           # [R] ids: row r scores element r, however the rows are cut into sequences
+        S = int(rows_shape[1]) if logits.dim() == 3 else (int(rows_per_seq) if rows_per_seq else max(R, 1))
+        step_stride = int(ids.stride(0))
+        seq_stride = S * step_stride
+    if R and (S < 1 or R % S or (rows_per_seq is not None and int(rows_per_seq) != S)):
+        raise _lib.SelftokHipError(f"{what}: rows_per_seq {rows_per_seq} does not go with {R} rows and ids {tuple(ids.shape)}")
+    ids_ptr = _p(ids)
+    if reverse_steps:
+        ids_ptr += (S - 1) * step_stride * ids.element_size()
+        step_stride = -step_stride
+    dev = logits.device
+    logprob = _out(what, logprob, torch.float32, rows_shape, dev, "logprob")
+    mass = _out(what, mass, torch.int64, rows_shape + (2,), dev, "mass")
+    rank = _out(what, rank, torch.int32, rows_shape, dev, "rank")
+    top_id = _out(what, top_id, torch.int32, rows_shape, dev, "top_id")
+    entropy = _out(what, entropy, torch.float32, rows_shape, dev, "entropy")
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if ignored is None:
+        ignored = torch.zeros(1, dtype=torch.int32, device=dev)
+    _token_u32(what, "bad", bad, (1,))
+    _token_u32(what, "ignored", ignored, (1,))
+    if not temperature > 0.0:
+        raise _lib.SelftokHipError(f"{what}: need a temperature > 0 (a greedy distribution has no log-probabilities), got {temperature}")
+    if R:
+        _lib.check(_lib.load().selftok_score_tokens(_p(logits), _p(uncond_logits), _SAMPLE_DTYPES[logits.dtype], R, C, rs, offset, float(cfg_scale), float(temperature),
+                                                    ids_ptr, ids.element_size(), S, seq_stride, step_stride, _p(logprob), _p(mass), _p(rank), _p(top_id), _p(entropy),
+                                                    _p(bad), _p(ignored), _stream()), "selftok_score_tokens")
+    return logprob, mass, rank, top_id, entropy, bad, ignored

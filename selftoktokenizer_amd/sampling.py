@@ -13,6 +13,9 @@ and that sample's logits alone: the same request gives the same ids alone or in 
         if s % 64 == 63:
             ids, m = sampler.partial()
             preview = pipe.decoding(ids, ar_partial=m)
+
+The teacher-forced side (csrc/token_score.hip, `ops.token_score`): `score_tokens(logits[B, S, V], ids[B, K])` gives a `TokenScore` -- the log-probability,
+rank and entropy of every known id under the same arithmetic, and NLL / perplexity / top-k accuracy / per-position NLL over them.
 """
 from __future__ import annotations
 
@@ -127,3 +130,84 @@ class TokenSampler:
         self.n_kept.copy_(torch.from_numpy(np.asarray(st["n_kept"], dtype=np.int32)))
         self.bad.fill_(int(st["bad"]))
         return self
+
+
+# ---- the teacher-forced side: what did the model give ids that are already known? (csrc/token_score.hip, `ops.token_score`) ----
+class TokenScore:
+    """The device tensors of one `score_tokens` call, [B, S] each (mass [B, S, 2] holds the uint64 (Q_total, q_t) in int64), the two counters, and
+    `positions` [S]: the tokenizer position column s was scored against.  The reductions below are torch fp64 on the device and return 0-d / 1-d fp64
+    tensors; they leave out ignored rows (rank -1) and REFUSE to summarise while bad > 0 (one read-back) unless allow_bad=True, which leaves bad rows
+    out as well."""
+
+    def __init__(self, logprob, mass, rank, top_id, entropy, bad, ignored, positions, K):
+        self.logprob, self.mass, self.rank, self.top_id, self.entropy, self.bad, self.ignored = logprob, mass, rank, top_id, entropy, bad, ignored
+        self.positions, self.K = np.asarray(positions, dtype=np.int64), int(K)
+
+    def _scored(self, allow_bad: bool) -> torch.Tensor:
+        n_bad = int(self.bad.reshape(-1)[0])
+        if n_bad > 0 and not allow_bad:
+            raise ValueError(f"{n_bad} bad rows (NaN / +inf / all -inf logits, or a target outside the window): pass allow_bad=True to summarise the rest")
+        return self.rank >= 0                                        # ignored and bad rows both carry rank -1
+
+    def _lp(self, ok):
+        return torch.where(ok, self.logprob.double(), torch.zeros((), dtype=torch.float64, device=self.logprob.device))
+
+    def sequence_logprob(self, allow_bad: bool = False) -> torch.Tensor:
+        """[B]: the sum of the scored rows' log-probabilities per sequence"""
+        return self._lp(self._scored(allow_bad)).sum(dim=1)
+
+    def nll(self, allow_bad: bool = False) -> torch.Tensor:
+        """the mean negative log-probability per scored token (NaN when none was scored)"""
+        ok = self._scored(allow_bad)
+        return -self._lp(ok).sum() / ok.sum().double()
+
+    def perplexity(self, allow_bad: bool = False) -> torch.Tensor:
+        return torch.exp(self.nll(allow_bad))
+
+    def per_position_nll(self, allow_bad: bool = False) -> torch.Tensor:
+        """[K], indexed by TOKENIZER position; NaN where no row was scored"""
+        ok = self._scored(allow_bad)
+        col = -self._lp(ok).sum(dim=0) / ok.sum(dim=0).double()
+        out = torch.full((self.K,), float("nan"), dtype=torch.float64, device=col.device)
+        out[torch.from_numpy(self.positions).to(col.device)] = col
+        return out
+
+    def topk_accuracy(self, k: int = 1, allow_bad: bool = False) -> torch.Tensor:
+        """the share of scored rows whose target sits at rank < k"""
+        ok = self._scored(allow_bad)
+        return (ok & (self.rank < int(k))).sum().double() / ok.sum().double()
+
+    def mean_rank(self, allow_bad: bool = False) -> torch.Tensor:
+        ok = self._scored(allow_bad)
+        return torch.where(ok, self.rank, torch.zeros_like(self.rank)).double().sum() / ok.sum().double()
+
+    def mean_entropy(self, allow_bad: bool = False) -> torch.Tensor:
+        ok = self._scored(allow_bad)
+        return torch.where(ok, self.entropy.double(), torch.zeros((), dtype=torch.float64, device=self.entropy.device)).sum() / ok.sum().double()
+
+
+def score_tokens(logits: torch.Tensor, ids: torch.Tensor, *, ar_order: bool = True, steps=None, uncond_logits: Optional[torch.Tensor] = None,
+                 C: Optional[int] = None, offset: int = 0, cfg_scale: Optional[float] = None, temperature: float = 1.0, ops=None) -> TokenScore:
+    """logits [B, S, V] (fp32 or bf16) the model produced for the KNOWN ids [B, K] (int32 / int64, tokenizer order, any column stride), S <= K.
+    ar_order=True: logits row s is AR step s and scores tokenizer position K - 1 - s, so the S steps are positions K - S .. K - 1 -- the ids and step count
+    of `TokenSampler.partial()` go in as they are, and nothing is flipped or copied.  ar_order=False: row s scores position s.  steps: an int or one count
+    per sequence, as partial()'s m: rows at or past a sequence's count are IGNORED (this builds one [B, S] id tensor; ids that are negative already are
+    ignored without it).  cfg_scale goes with uncond_logits, both or neither.  Reads nothing back."""
+    o = _ops if ops is None else ops
+    if logits.dim() != 3 or ids.dim() != 2 or ids.shape[0] != logits.shape[0] or logits.shape[1] > ids.shape[1]:
+        raise ValueError(f"need logits [B, S, V] and ids [B, K] with S <= K, got {tuple(logits.shape)} and {tuple(ids.shape)}")
+    if (uncond_logits is None) != (cfg_scale is None):
+        raise ValueError("unconditional logits go with a cfg_scale: pass both or neither")
+    B, S, _ = logits.shape
+    K = ids.shape[1]
+    positions = (K - 1 - np.arange(S)) if ar_order else np.arange(S)
+    view = ids[:, K - S:] if ar_order else ids[:, :S]               # [B, S] in tokenizer order; reverse_steps walks it backwards
+    reverse = bool(ar_order)
+    if steps is not None:
+        st = torch.as_tensor(np.broadcast_to(np.asarray(steps, dtype=np.int64).reshape(-1), (B,)).copy(), device=ids.device)
+        tgt = view.flip(1) if reverse else view                     # row order
+        live = torch.arange(S, device=ids.device).unsqueeze(0) < st.unsqueeze(1)
+        view, reverse = torch.where(live, tgt, torch.full_like(tgt, -1)), False
+    out = o.token_score(logits, view, uncond_logits=uncond_logits, C=C, offset=offset, cfg_scale=1.0 if cfg_scale is None else float(cfg_scale),
+                        temperature=float(temperature), reverse_steps=reverse)
+    return TokenScore(*out, positions=positions, K=K)
