@@ -473,6 +473,41 @@ int selftok_score_tokens(const void* logits, const void* uncond_logits, int dtyp
                          const void* ids, int id_bytes, int rows_per_seq, long id_seq_stride, long id_step_stride, float* logprob, unsigned long long* mass,
                          int* rank, int* top_id, float* entropy, unsigned* bad, unsigned* ignored, hipStream_t stream);
 
+/* ---- token loss: AR logits over a window of C codes and a KNOWN id per row -> cross-entropy, log-sum-exp and the gradient row (csrc/token_xent.hip) ----
+ * The training side of the scorer above, on its arithmetic at temperature 1 without guidance: l is the logit itself (l * 1.0f is exact), and steps 3 - 4 of
+ * the sampler's text hold word for word (the key, -0.0 = +0.0, the row maximum m, the integer mass q_i with the same constants, q = 0 for d < -24, exactly
+ * 2^32 at the maximum, Q_total their integer sum), so that nll is the scorer's logprob with the sign turned, bit for bit (tests/token_xent_cases.py restates
+ * the rest in numpy).  Stateless and capturable, no workspace, no synchronisation; every refusal is decided on the host before the launch (SELFTOK_EINVAL
+ * with a message) and leaves the outputs untouched.  A row's outputs depend on that row's inputs alone.
+ *
+ * Inputs.  logits, dtype, R, C, row_stride, offset, ids, id_bytes, rows_per_seq, id_seq_stride, id_step_stride: the scorer's layout, alignment, window and
+ *   target-addressing rules.  V: the columns of a gradient row, offset + C <= V <= row_stride (and V <= grad_stride).  row_scale: fp32 dense [R] or null
+ *   (1.0 for every row): the upstream scale g of the row -- weight / number of scored rows for a mean.  z_coef: finite, >= 0: the coefficient of the
+ *   auxiliary term z_coef * lse^2.
+ * Outputs.
+ *   lse fp32 [R]: L = (double) m + log((double) Q_total * 2^-32), fp64; lse = (float) L, rounded once.
+ *   nll fp32 [R] = (float) -(((double) l_t - (double) m) - log((double) Q_total * 2^-32)): the scorer's logprob with the sign bit turned (-0.0 where the
+ *     logprob is +0.0).  A target more than 24 below the maximum has q_t = 0 and still a finite nll; a target at -inf among finite logits gets +inf and is
+ *     NOT bad.
+ *   grad, the logits' dtype, row r at element r * grad_stride, V columns written: column offset + i, i in [0, C), gets a * p_i - (i == t ? g : 0) with
+ *     g = row_scale[r] (1.0f when null),
+ *     a = g * (float) (1.0 + (2.0 * (double) z_coef) * L)   -- the fp64 product 2 z first, then that times L, then the sum, each rounded on its own, one
+ *         rounding to fp32, one fp32 product; z_coef == 0 makes the factor exactly 1 and a == g,
+ *     p_i = (float) ((double) q_i * (1.0 / (double) Q_total))   -- one fp64 quotient per row, one fp64 product and one rounding per code,
+ *     the product a * p_i and the difference fp32, each rounded on its own (a column other than the target's subtracts +0.0, which changes no bit); bf16
+ *     output is rounded to nearest even once (a NaN, which only a NaN or infinite row_scale produces, stays a NaN).  Columns [0, offset) and
+ *     [offset + C, V) are written as +0; columns [V, grad_stride) are never touched.
+ * Row kinds.  IGNORED: a target < 0 on a row that is not bad: nll +0.0, lse as for any row, the gradient row all +0 AND WRITTEN, ignored[0] += 1.
+ *   BAD: a NaN or +inf logit in the window, nothing above -inf, or a target >= C: nll and lse NaN, bad[0] += 1, and the gradient row all +0 AND WRITTEN:
+ *   the NaN in nll is what turns the trainer's loss into NaN, while zero gradients keep one poisoned row from destroying the other rows' buffers.
+ *   bad and ignored accumulate: the caller zeroes them.
+ * In place.  grad == logits with grad_stride == row_stride is allowed and gives the out-of-place bits: the logits are gone afterwards.  Any other
+ *   intersection of the two extents (first to last addressed element of each) is refused.
+ * R == 0 returns 0 without a launch. */
+int selftok_xent_rows(const void* logits, int dtype, int R, int C, long row_stride, long offset, const void* ids, int id_bytes, int rows_per_seq,
+                      long id_seq_stride, long id_step_stride, long V, const float* row_scale, float z_coef, float* nll, float* lse, void* grad,
+                      long grad_stride, unsigned* bad, unsigned* ignored, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,96 @@
+"""The training loss over image tokens: cross-entropy of known ids under AR logits, with its gradient, in ONE launch of csrc/token_xent.hip
+(`ops.token_xent`; include/selftok_hip_ext.h states the arithmetic).  The forward pass writes `softmax - onehot`, already scaled by each row's share of
+the reduction, so the backward pass is one multiplication by the upstream gradient; with inplace=True that gradient is written over the logits and the loss
+costs one read and one write of them and no buffer of their size."""
+from collections import namedtuple
+from typing import Optional
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import ops as _ops
+from .sampling import target_view
+
+XentStats = namedtuple("XentStats", "nll lse bad ignored")
+REDUCTIONS = ("mean", "sum", "none")
+
+
+class _TokenXent(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, view, reverse, w, C, offset, z, reduction, inplace, o):
+        B, S = logits.shape[0], logits.shape[1]
+        dev = logits.device
+        tgt = view.flip(1) if reverse else view                     # [B, S] in row order: which rows are scored (B * S ids, not B * S * V logits)
+        scored = tgt >= 0
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        wd = None if w is None else w.double()
+        if reduction == "mean":                                     # the weight of the scored rows, counted on the device: nothing is read back
+            denom = scored.sum().double() if wd is None else torch.where(scored, wd, zero).sum()
+            scale = ((1.0 / denom) if wd is None else (wd / denom)).float().expand(B, S).contiguous()
+        else:
+            denom = None
+            scale = None if w is None else w.float().expand(B, S).contiguous()
+        nll, lse, grad, bad, ignored = o.token_xent(logits, view, C=C, offset=offset, z_coef=z, row_scale=scale, inplace=inplace, reverse_steps=reverse)
+        rows = nll.double() + z * lse.double() * lse.double() if z else nll.double()
+        rows = torch.where(scored, rows if wd is None else rows * wd, zero)        # an ignored row has nll 0 but an lse; a bad row keeps its NaN
+        if reduction == "none":
+            loss = rows.float()
+        elif reduction == "sum":
+            loss = rows.sum().float()
+        else:
+            loss = (rows.sum() / denom).float()
+        ctx.buf, ctx.per_row = grad, reduction == "none"
+        if inplace and hasattr(torch.autograd.graph, "increment_version"):
+            torch.autograd.graph.increment_version(logits)         # whoever saved the logits for its own backward must hear that they are gone
+        ctx.mark_non_differentiable(nll, lse, bad, ignored)
+        return loss, nll, lse, bad, ignored
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, *_):
+        buf = ctx.buf
+        if buf is None:
+            raise RuntimeError("token_cross_entropy: backward a second time: the gradient buffer was scaled by the first upstream gradient and handed over "
+                               "(run the forward pass again)")
+        ctx.buf = None
+        buf.mul_(g_loss.unsqueeze(-1) if ctx.per_row else g_loss)
+        return (buf,) + (None,) * 9
+
+
+def token_cross_entropy(logits: torch.Tensor, ids: torch.Tensor, *, ar_order: bool = True, steps=None, C: Optional[int] = None, offset: int = 0,
+                        z_loss: float = 0.0, weights: Optional[torch.Tensor] = None, reduction: str = "mean", inplace: bool = False,
+                        return_stats: bool = False, ops=None):
+    """Cross-entropy of the KNOWN ids [B, K] (int32 / int64, tokenizer order) under logits [B, S, V] (fp32 or bf16, S <= K) over the window
+    [offset, offset + C) of each row (default: the rest of the row), plus z_loss * logsumexp^2 per row, differentiable with respect to `logits`.
+    ar_order and steps mean what they mean in `sampling.score_tokens`: ar_order=True lets row s be AR step s and meet tokenizer position K - 1 - s without a
+    flipped copy; rows at or past a sequence's step count, and ids that are negative already, are IGNORED: no loss, a zero gradient row.
+    weights: [K], indexed by TOKENIZER position, or [B, S], one per row of `logits`.  reduction: "mean" (sum of w * loss over sum of w, over the scored
+    rows), "sum" or "none" ([B, S], 0 on ignored rows).  The gradient is computed IN THE FORWARD LAUNCH, scaled per row on the device (the count of scored
+    rows included: nothing is read back); `loss.backward()` multiplies that buffer by the upstream gradient and hands it to `logits.grad`.  One backward per
+    forward; double backward is refused.  inplace=True writes the gradient OVER `logits` and allocates nothing of their size: THE LOGITS ARE GONE AFTERWARDS,
+    so whatever else needs their values (another loss, a metric, an operation that saved them for its own backward) must come first or do without.
+    A row with a NaN / +inf / all -inf window or an id >= C is BAD: its loss is NaN -- so "mean" and "sum" are NaN -- and its gradient row is zero.
+    The scalar is formed from nll and lse in fp64 on the device and returned as fp32.  return_stats=True: -> (loss, XentStats(nll [B, S], lse [B, S], bad [1],
+    ignored [1])), device tensors."""
+    o = _ops if ops is None else ops
+    if logits.dim() != 3 or ids.dim() != 2 or ids.shape[0] != logits.shape[0] or logits.shape[1] > ids.shape[1]:
+        raise ValueError(f"need logits [B, S, V] and ids [B, K] with S <= K, got {tuple(logits.shape)} and {tuple(ids.shape)}")
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"reduction must be one of {REDUCTIONS}, got {reduction!r}")
+    z = float(z_loss)
+    if not (z >= 0.0 and z != float("inf")):
+        raise ValueError(f"need a finite z_loss >= 0, got {z_loss}")
+    B, S, _ = logits.shape
+    K = ids.shape[1]
+    view, reverse, positions = target_view(ids, S, ar_order, steps)
+    w = None
+    if weights is not None:
+        if tuple(weights.shape) == (K,):
+            w = weights.index_select(0, torch.as_tensor(positions, device=weights.device)).unsqueeze(0)      # [1, S]: the weight of the position row s meets
+        elif tuple(weights.shape) == (B, S):
+            w = weights
+        else:
+            raise ValueError(f"weights must be [K] = [{K}] by tokenizer position or [B, S] = [{B}, {S}] by row, got {tuple(weights.shape)}")
+        w = w.detach()
+    loss, nll, lse, bad, ignored = _TokenXent.apply(logits, view, reverse, w, C, int(offset), z, reduction, bool(inplace), o)
+    return (loss, XentStats(nll, lse, bad, ignored)) if return_stats else loss

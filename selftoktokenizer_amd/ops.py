@@ -1933,22 +1933,9 @@ def token_sample(logits: torch.Tensor, ctr: torch.Tensor, ids_out: torch.Tensor,
 # ----------------------------------------------------------------------------------------------
 # token scorer (csrc/token_score.hip): AR logits and KNOWN ids -> log-probability, rank, first code, entropy per row
 # ----------------------------------------------------------------------------------------------
-def token_score(logits: torch.Tensor, ids: torch.Tensor, *, uncond_logits: Optional[torch.Tensor] = None, C: Optional[int] = None, offset: int = 0,
-                cfg_scale: float = 1.0, temperature: float = 1.0, rows_per_seq: Optional[int] = None, reverse_steps: bool = False,
-                logprob: Optional[torch.Tensor] = None, mass: Optional[torch.Tensor] = None, rank: Optional[torch.Tensor] = None,
-                top_id: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None,
-                ignored: Optional[torch.Tensor] = None):
-    """Teacher-forced scores of known ids: `logits` [R, V] or [B, S, V] (fp32 or bf16, unit code stride, row stride a multiple of 4 codes; [B, S, V] must
-    flatten to rows without a copy) over the window [offset, offset + C) (default: the rest of the row), with the sampler's guidance (`uncond_logits`,
-    `cfg_scale`) and `temperature` > 0 -- include/selftok_hip_ext.h states the arithmetic, the sampler's own.  `ids`: int32 or int64, [R] or [B, S] (R = B * S),
-    ANY strided view (a column range of a wider [B, K] matrix, every other column, an expanded row): the two id strides are taken from it and nothing is
-    copied.  `reverse_steps` reads the steps of a sequence backwards -- row (b, s) scores ids[b, S - 1 - s] -- which is how AR-ordered logits meet
-    tokenizer-ordered ids (torch has no negative strides; the kernel has).  `rows_per_seq`, if given, must be the S so derived.  A target is 0-based inside
-    the window; a target < 0 is IGNORED (padding), a target >= C makes the row BAD, as does a NaN / +inf / all -inf row.
-    -> (logprob fp32, mass int64 [..., 2] holding the uint64 (Q_total, q_t), rank int32, top_id int32, entropy fp32, bad 32-bit [1], ignored 32-bit [1]), the
-    row outputs shaped [R] or [B, S]; bad and ignored ACCUMULATE.  Preallocated outputs are taken as given.  No synchronisation, nothing read back."""
-    _need_cuda(logits, uncond_logits, ids, logprob, mass, rank, top_id, entropy, bad, ignored)
-    what = "token_score"
+def _token_rows(what: str, logits: torch.Tensor, ids: torch.Tensor, C, offset, rows_per_seq, reverse_steps):
+    """the row layout one scorer / loss call hands to its kernel: `logits` [R, V] or [B, S, V] flattened to rows without a copy, the window, and the targets'
+    addressing taken from the strides of `ids` -> (rows_shape, R, V, C, offset, row_stride, S, id_seq_stride, id_step_stride, ids_ptr)"""
     if logits.dtype not in _SAMPLE_DTYPES or logits.dim() not in (2, 3):
         raise _lib.SelftokHipError(f"{what}: `logits` must be fp32 or bf16 [R, V] or [B, S, V], got {logits.dtype} {tuple(logits.shape)}")
     V = logits.shape[-1]
@@ -1973,9 +1960,6 @@ def token_score(logits: torch.Tensor, ids: torch.Tensor, *, uncond_logits: Optio
         rs = logits.stride(0)
     if R <= 1:
         rs = max(V, rs)
-    if uncond_logits is not None and (uncond_logits.dtype != logits.dtype or uncond_logits.shape != logits.shape or (R > 1 and uncond_logits.stride() != logits.stride())
-                                      or uncond_logits.stride(-1) != 1):
-        raise _lib.SelftokHipError(f"{what}: `uncond_logits` must have the dtype, shape and strides of `logits`")
     if ids.dtype not in (torch.int32, torch.int64) or ids.dim() not in (1, 2) or ids.numel() != R or (logits.dim() == 3 and ids.dim() == 2 and tuple(ids.shape) != rows_shape):
         raise _lib.SelftokHipError(f"{what}: `ids` must be int32 or int64, [R] or [B, S] with one id per row of `logits` ({R}), got {ids.dtype} {tuple(ids.shape)}")
     if ids.dim() == 2:
@@ -1990,6 +1974,29 @@ def token_score(logits: torch.Tensor, ids: torch.Tensor, *, uncond_logits: Optio
     if reverse_steps:
         ids_ptr += (S - 1) * step_stride * ids.element_size()
         step_stride = -step_stride
+    return rows_shape, R, V, C, offset, rs, S, seq_stride, step_stride, ids_ptr
+
+
+def token_score(logits: torch.Tensor, ids: torch.Tensor, *, uncond_logits: Optional[torch.Tensor] = None, C: Optional[int] = None, offset: int = 0,
+                cfg_scale: float = 1.0, temperature: float = 1.0, rows_per_seq: Optional[int] = None, reverse_steps: bool = False,
+                logprob: Optional[torch.Tensor] = None, mass: Optional[torch.Tensor] = None, rank: Optional[torch.Tensor] = None,
+                top_id: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None,
+                ignored: Optional[torch.Tensor] = None):
+    """Teacher-forced scores of known ids: `logits` [R, V] or [B, S, V] (fp32 or bf16, unit code stride, row stride a multiple of 4 codes; [B, S, V] must
+    flatten to rows without a copy) over the window [offset, offset + C) (default: the rest of the row), with the sampler's guidance (`uncond_logits`,
+    `cfg_scale`) and `temperature` > 0 -- include/selftok_hip_ext.h states the arithmetic, the sampler's own.  `ids`: int32 or int64, [R] or [B, S] (R = B * S),
+    ANY strided view (a column range of a wider [B, K] matrix, every other column, an expanded row): the two id strides are taken from it and nothing is
+    copied.  `reverse_steps` reads the steps of a sequence backwards -- row (b, s) scores ids[b, S - 1 - s] -- which is how AR-ordered logits meet
+    tokenizer-ordered ids (torch has no negative strides; the kernel has).  `rows_per_seq`, if given, must be the S so derived.  A target is 0-based inside
+    the window; a target < 0 is IGNORED (padding), a target >= C makes the row BAD, as does a NaN / +inf / all -inf row.
+    -> (logprob fp32, mass int64 [..., 2] holding the uint64 (Q_total, q_t), rank int32, top_id int32, entropy fp32, bad 32-bit [1], ignored 32-bit [1]), the
+    row outputs shaped [R] or [B, S]; bad and ignored ACCUMULATE.  Preallocated outputs are taken as given.  No synchronisation, nothing read back."""
+    _need_cuda(logits, uncond_logits, ids, logprob, mass, rank, top_id, entropy, bad, ignored)
+    what = "token_score"
+    rows_shape, R, V, C, offset, rs, S, seq_stride, step_stride, ids_ptr = _token_rows(what, logits, ids, C, offset, rows_per_seq, reverse_steps)
+    if uncond_logits is not None and (uncond_logits.dtype != logits.dtype or uncond_logits.shape != logits.shape or (R > 1 and uncond_logits.stride() != logits.stride())
+                                      or uncond_logits.stride(-1) != 1):
+        raise _lib.SelftokHipError(f"{what}: `uncond_logits` must have the dtype, shape and strides of `logits`")
     dev = logits.device
     logprob = _out(what, logprob, torch.float32, rows_shape, dev, "logprob")
     mass = _out(what, mass, torch.int64, rows_shape + (2,), dev, "mass")
@@ -2009,3 +2016,55 @@ def token_score(logits: torch.Tensor, ids: torch.Tensor, *, uncond_logits: Optio
                                                     ids_ptr, ids.element_size(), S, seq_stride, step_stride, _p(logprob), _p(mass), _p(rank), _p(top_id), _p(entropy),
                                                     _p(bad), _p(ignored), _stream()), "selftok_score_tokens")
     return logprob, mass, rank, top_id, entropy, bad, ignored
+
+
+# ----------------------------------------------------------------------------------------------
+# token loss (csrc/token_xent.hip): AR logits and KNOWN ids -> cross-entropy, log-sum-exp and the gradient row
+# ----------------------------------------------------------------------------------------------
+def token_xent(logits: torch.Tensor, ids: torch.Tensor, *, C: Optional[int] = None, offset: int = 0, z_coef: float = 0.0, row_scale: Optional[torch.Tensor] = None,
+               grad: Optional[torch.Tensor] = None, inplace: bool = False, reverse_steps: bool = False, rows_per_seq: Optional[int] = None,
+               nll: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None, ignored: Optional[torch.Tensor] = None):
+    """Cross-entropy of known ids and its gradient in one launch: `logits` and `ids` exactly as `token_score` takes them (shapes, strides, window,
+    `reverse_steps`), at temperature 1 without guidance -- include/selftok_hip_ext.h states the arithmetic.  Row r gets nll = -log softmax(l)[t], lse = log sum
+    exp(l) and the gradient row `a * softmax(l) - g * onehot(t)` of g * (nll + z_coef * lse^2), g = row_scale[r] (fp32, one per row, shaped as the rows; None: 1)
+    and a = g * (1 + 2 * z_coef * lse), over all V columns of the row: zero outside the window.  `grad`: a tensor of the logits' shape and dtype with unit code
+    stride and rows that flatten as the logits' do (default: a new contiguous one); inplace=True writes the gradient OVER `logits` instead, the same bits, and
+    allocates nothing of that size -- the logits are gone afterwards.  An IGNORED row (target < 0) has nll 0 and a zero gradient row; a BAD row (NaN / +inf /
+    all -inf, or a target >= C) has nll and lse NaN and a zero gradient row.
+    -> (nll fp32, lse fp32, grad, bad 32-bit [1], ignored 32-bit [1]); nll and lse shaped [R] or [B, S]; bad and ignored ACCUMULATE.  No synchronisation,
+    nothing read back."""
+    _need_cuda(logits, ids, row_scale, grad, nll, lse, bad, ignored)
+    what = "token_xent"
+    rows_shape, R, V, C, offset, rs, S, seq_stride, step_stride, ids_ptr = _token_rows(what, logits, ids, C, offset, rows_per_seq, reverse_steps)
+    z_coef = float(z_coef)
+    if not (z_coef >= 0.0 and z_coef != float("inf")):
+        raise _lib.SelftokHipError(f"{what}: need a finite z_coef >= 0, got {z_coef}")
+    if inplace:
+        if grad is not None and grad is not logits:
+            raise _lib.SelftokHipError(f"{what}: inplace=True writes the gradient over `logits`: pass no `grad`")
+        grad, gs = logits, rs
+    else:
+        if grad is None:
+            grad = torch.empty(tuple(logits.shape), dtype=logits.dtype, device=logits.device)
+        if grad.dtype != logits.dtype or grad.shape != logits.shape or (V and grad.stride(-1) != 1) or \
+                (grad.dim() == 3 and R > 1 and grad.shape[0] > 1 and grad.shape[1] > 1 and grad.stride(0) != grad.shape[1] * grad.stride(1)):
+            raise _lib.SelftokHipError(f"{what}: `grad` must have the dtype and shape of `logits`, unit code stride and rows that flatten without a copy, got "
+                                       f"{grad.dtype} {tuple(grad.shape)} strides {grad.stride()}")
+        gs = grad.stride(-2) if (grad.dim() == 2 or grad.shape[1] > 1) else grad.stride(0)
+        if R <= 1:
+            gs = max(V, gs)
+    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.numel() != R or not row_scale.is_contiguous()):
+        raise _lib.SelftokHipError(f"{what}: `row_scale` must be a contiguous fp32 tensor with one element per row ({R}), got {row_scale.dtype} {tuple(row_scale.shape)}")
+    dev = logits.device
+    nll = _out(what, nll, torch.float32, rows_shape, dev, "nll")
+    lse = _out(what, lse, torch.float32, rows_shape, dev, "lse")
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if ignored is None:
+        ignored = torch.zeros(1, dtype=torch.int32, device=dev)
+    _token_u32(what, "bad", bad, (1,))
+    _token_u32(what, "ignored", ignored, (1,))
+    if R:
+        _lib.check(_lib.load().selftok_xent_rows(_p(logits), _SAMPLE_DTYPES[logits.dtype], R, C, rs, offset, ids_ptr, ids.element_size(), S, seq_stride, step_stride, V,
+                                                 _p(row_scale), z_coef, _p(nll), _p(lse), _p(grad), gs, _p(bad), _p(ignored), _stream()), "selftok_xent_rows")
+    return nll, lse, grad, bad, ignored

@@ -186,6 +186,23 @@ class TokenScore:
         return torch.where(ok, self.entropy.double(), torch.zeros((), dtype=torch.float64, device=self.entropy.device)).sum() / ok.sum().double()
 
 
+def target_view(ids: torch.Tensor, S: int, ar_order: bool, steps):
+    """How S rows of logits meet ids [B, K] in tokenizer order (shared by `score_tokens` and `losses.token_cross_entropy`) -> (view [B, S], reverse, positions
+    [S]).  ar_order=True: row s is AR step s and meets tokenizer position K - 1 - s; the view is the last S columns, in tokenizer order, to be walked backwards
+    (reverse=True) -- nothing is flipped or copied.  ar_order=False: row s meets position s.  steps (an int or one count per sequence): rows at or past a
+    sequence's count get the target -1; this builds one [B, S] tensor in row order (reverse=False)."""
+    B, K = ids.shape
+    positions = (K - 1 - np.arange(S)) if ar_order else np.arange(S)
+    view = ids[:, K - S:] if ar_order else ids[:, :S]               # [B, S] in tokenizer order; reverse_steps walks it backwards
+    reverse = bool(ar_order)
+    if steps is not None:
+        st = torch.as_tensor(np.broadcast_to(np.asarray(steps, dtype=np.int64).reshape(-1), (B,)).copy(), device=ids.device)
+        tgt = view.flip(1) if reverse else view                     # row order
+        live = torch.arange(S, device=ids.device).unsqueeze(0) < st.unsqueeze(1)
+        view, reverse = torch.where(live, tgt, torch.full_like(tgt, -1)), False
+    return view, reverse, positions
+
+
 def score_tokens(logits: torch.Tensor, ids: torch.Tensor, *, ar_order: bool = True, steps=None, uncond_logits: Optional[torch.Tensor] = None,
                  C: Optional[int] = None, offset: int = 0, cfg_scale: Optional[float] = None, temperature: float = 1.0, ops=None) -> TokenScore:
     """logits [B, S, V] (fp32 or bf16) the model produced for the KNOWN ids [B, K] (int32 / int64, tokenizer order, any column stride), S <= K.
@@ -198,16 +215,8 @@ def score_tokens(logits: torch.Tensor, ids: torch.Tensor, *, ar_order: bool = Tr
         raise ValueError(f"need logits [B, S, V] and ids [B, K] with S <= K, got {tuple(logits.shape)} and {tuple(ids.shape)}")
     if (uncond_logits is None) != (cfg_scale is None):
         raise ValueError("unconditional logits go with a cfg_scale: pass both or neither")
-    B, S, _ = logits.shape
     K = ids.shape[1]
-    positions = (K - 1 - np.arange(S)) if ar_order else np.arange(S)
-    view = ids[:, K - S:] if ar_order else ids[:, :S]               # [B, S] in tokenizer order; reverse_steps walks it backwards
-    reverse = bool(ar_order)
-    if steps is not None:
-        st = torch.as_tensor(np.broadcast_to(np.asarray(steps, dtype=np.int64).reshape(-1), (B,)).copy(), device=ids.device)
-        tgt = view.flip(1) if reverse else view                     # row order
-        live = torch.arange(S, device=ids.device).unsqueeze(0) < st.unsqueeze(1)
-        view, reverse = torch.where(live, tgt, torch.full_like(tgt, -1)), False
+    view, reverse, positions = target_view(ids, logits.shape[1], ar_order, steps)
     out = o.token_score(logits, view, uncond_logits=uncond_logits, C=C, offset=offset, cfg_scale=1.0 if cfg_scale is None else float(cfg_scale),
                         temperature=float(temperature), reverse_steps=reverse)
     return TokenScore(*out, positions=positions, K=K)
