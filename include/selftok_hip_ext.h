@@ -508,6 +508,49 @@ int selftok_xent_rows(const void* logits, int dtype, int R, int C, long row_stri
                       long id_seq_stride, long id_step_stride, long V, const float* row_scale, float z_coef, float* nll, float* lse, void* grad,
                       long grad_stride, unsigned* bad, unsigned* ignored, hipStream_t stream);
 
+/* ---- token distillation: STUDENT logits and TEACHER logits over one window of C codes -> KL(teacher || student), soft cross-entropy, teacher entropy,
+ *      student log-sum-exp and the gradient row (csrc/token_distill.hip) ----
+ * The full-distribution side of the loss above, on its arithmetic at temperature 1 on both sides: steps 3 - 4 of the sampler's text hold word for word for
+ * EITHER row (the key, -0.0 = +0.0, the row maximum, the integer mass q_i with the same constants, q = 0 for d < -24, exactly 2^32 at the maximum, the
+ * integer sum of the masses), and the teacher's entropy is the scorer's, bit for bit (tests/token_distill_cases.py restates the rest in numpy).  Stateless
+ * and capturable, no workspace, no synchronisation; every refusal is decided on the host before the launch (SELFTOK_EINVAL with a message) and leaves the
+ * outputs untouched.  A row's outputs depend on that row's inputs alone.
+ *
+ * Inputs.  student, dtype, R, C, row_stride, offset, V, row_scale, grad, grad_stride: the loss's layout, alignment, window and refusal rules.  teacher:
+ *   teacher_dtype 0 = fp32, 1 = bf16, independent of the student's; row r holds the same window at elements r * teacher_stride + offset .. + C - 1; the
+ *   pointer is aligned to four codes of ITS dtype and (for R > 1) teacher_stride is a multiple of 4.  teacher_uncond: null, or the teacher's dtype, stride
+ *   and alignment; then the teacher logit is the sampler's step 1 word for word, a_i = lu + s * (lc - lu), s = cfg_scale (finite): difference, product,
+ *   sum, each rounded to fp32; teacher is lc.  Otherwise a_i is the teacher's logit itself.  b_i is the student's logit.  row_scale: fp32 [R] or null
+ *   (1.0).  row_mask: uint8 [R] or null; a 0 makes the row IGNORED.  grad: the student's dtype, or NULL: metrics only -- nothing of a gradient is written,
+ *   V and grad_stride are not looked at.
+ * Teacher: maximum mA, dA_i = a_i - mA (fp32), masses qA_i, sum QA.  Student: maximum mB, masses qB_i, sum QB.  LA = log((double) QA * 2^-32), LB likewise.
+ * Outputs, fp32 dense [R], each one rounding of an fp64 value:
+ *   lse_student = (float) ((double) mB + LB).
+ *   h_teacher = (float) (LA + E_A), E_A = (double) S_A / (65536.0 * (double) QA), S_A = sum hA_i, hA_i = (uint64) trunc((double) qA_i * (double) (-dA_i) *
+ *     65536.0) for qA_i > 0, else 0: the scorer's entropy of the teacher row.
+ *   Cross term: x_i = (double) mB - (double) b_i, ONE fp64 subtraction of the two fp32 values (not the fp32 d the mass uses; the scorer's logprob is formed
+ *     the same way); c_i = (uint64) trunc(((double) qA_i * x_i) * 65536.0) where qA_i > 0, else 0 (the fp64 product first, then the exact scaling, then the
+ *     truncation).  A code with qA_i > 0 and x_i >= 32768.0 (+inf included: a student at -inf where the teacher has mass) sets the row's OVERFLOW flag and
+ *     contributes c_i = 0.  S_lo = sum (c_i & 0xFFFFFFFF), S_hi = sum (c_i >> 32): two uint64 sums, each below 2^48 at 65536 codes, any order the same bits.
+ *     X = (double) S_hi * 4294967296.0 + (double) S_lo; E_X = X / (65536.0 * (double) QA).
+ *   ce = (float) (LB + E_X): the cross-entropy of the student under the teacher's distribution.
+ *   kl = (float) (((LB - LA) + E_X) - E_A), not clamped at 0.  An OVERFLOW row gets ce = kl = +inf; it is NOT bad, and its gradient follows the formula.
+ *   grad, row r at element r * grad_stride, V columns written: column offset + i gets g * (pB_i - pA_i), g = row_scale[r] (1.0f when null),
+ *     pA_i = (float) ((double) qA_i * (1.0 / (double) QA)), pB_i likewise -- one fp64 quotient per row and side, one fp64 product and one rounding per code --
+ *     the difference and the product fp32, each rounded on its own; bf16 output is rounded to nearest even once.  Columns [0, offset) and [offset + C, V)
+ *     are written as +0; columns [V, grad_stride) are never touched.  This is the gradient of g * KL(teacher || student) with respect to the student logits.
+ * Row kinds.  IGNORED (row_mask[r] == 0): the four outputs +0.0, the gradient row all +0 AND WRITTEN, ignored[0] += 1; no logit of the row is read.
+ *   BAD, a row that is not ignored: a NaN or +inf in the window of student, teacher or teacher_uncond, or in the guided a_i (-inf in both teacher inputs
+ *   gives NaN), or a_i or b_i with nothing above -inf: the four outputs NaN, the gradient row all +0 AND WRITTEN, bad[0] += 1.  NaN outside the window makes
+ *   no row bad.  bad and ignored accumulate: the caller zeroes them.
+ * In place.  grad == student with grad_stride == row_stride is allowed and gives the out-of-place bits: the student logits are gone afterwards.  Any other
+ *   intersection of grad's extent with the student's (first to last addressed element of each), and ANY intersection with the extent of teacher or
+ *   teacher_uncond, is refused.
+ * R == 0 returns 0 without a launch. */
+int selftok_distill_rows(const void* student, int dtype, const void* teacher, const void* teacher_uncond, int teacher_dtype, int R, int C, long row_stride,
+                         long teacher_stride, long offset, float cfg_scale, long V, const float* row_scale, const unsigned char* row_mask, float* kl, float* ce,
+                         float* h_teacher, float* lse_student, void* grad, long grad_stride, unsigned* bad, unsigned* ignored, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

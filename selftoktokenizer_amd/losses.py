@@ -94,3 +94,93 @@ def token_cross_entropy(logits: torch.Tensor, ids: torch.Tensor, *, ar_order: bo
         w = w.detach()
     loss, nll, lse, bad, ignored = _TokenXent.apply(logits, view, reverse, w, C, int(offset), z, reduction, bool(inplace), o)
     return (loss, XentStats(nll, lse, bad, ignored)) if return_stats else loss
+
+
+# ---- distillation: KL(teacher || student) over the whole window, csrc/token_distill.hip through `ops.token_distill` ----
+DistillStats = namedtuple("DistillStats", "kl ce h_teacher lse bad ignored")
+
+
+class _TokenDistill(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, student, teacher, uncond, s, live, w, C, offset, reduction, inplace, o):
+        B, S = student.shape[0], student.shape[1]
+        dev = student.device
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        wd = None if w is None else w.double()
+        mask = None if live is None else live.to(torch.uint8).contiguous()
+        if reduction == "mean":                                     # the weight of the live rows, counted on the device: nothing is read back
+            if live is None:
+                denom = torch.full((), float(B * S), dtype=torch.float64, device=dev) if wd is None else wd.expand(B, S).sum()
+            else:
+                denom = live.sum().double() if wd is None else torch.where(live, wd, zero).sum()
+            scale = ((1.0 / denom) if wd is None else (wd / denom)).float().expand(B, S).contiguous()
+        else:
+            denom = None
+            scale = None if w is None else w.float().expand(B, S).contiguous()
+        kl, ce, h, lse, grad, bad, ignored = o.token_distill(student, teacher, teacher_uncond=uncond, cfg_scale=s, C=C, offset=offset, row_scale=scale, row_mask=mask,
+                                                             inplace=inplace)
+        rows = kl.double() if wd is None else kl.double() * wd      # an ignored row has kl 0; a bad row keeps its NaN
+        if live is not None:
+            rows = torch.where(live, rows, zero)
+        if reduction == "none":
+            loss = rows.float()
+        elif reduction == "sum":
+            loss = rows.sum().float()
+        else:
+            loss = (rows.sum() / denom).float()
+        ctx.buf, ctx.per_row = grad, reduction == "none"
+        if inplace and hasattr(torch.autograd.graph, "increment_version"):
+            torch.autograd.graph.increment_version(student)        # whoever saved the logits for its own backward must hear that they are gone
+        ctx.mark_non_differentiable(kl, ce, h, lse, bad, ignored)
+        return loss, kl, ce, h, lse, bad, ignored
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, *_):
+        buf = ctx.buf
+        if buf is None:
+            raise RuntimeError("token_distillation: backward a second time: the gradient buffer was scaled by the first upstream gradient and handed over "
+                               "(run the forward pass again)")
+        ctx.buf = None
+        buf.mul_(g_loss.unsqueeze(-1) if ctx.per_row else g_loss)
+        return (buf,) + (None,) * 10
+
+
+def token_distillation(student_logits: torch.Tensor, teacher_logits: torch.Tensor, *, teacher_uncond: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
+                       steps=None, ar_order: bool = True, weights: Optional[torch.Tensor] = None, reduction: str = "mean", C: Optional[int] = None, offset: int = 0,
+                       inplace: bool = False, return_stats: bool = False, ops=None):
+    """KL(teacher || student) between two full next-token distributions over the window [offset, offset + C) of each row, differentiable with respect to
+    `student_logits` [B, S, V] (fp32 or bf16).  `teacher_logits` has the same shape and its own dtype; with `teacher_uncond` the teacher is the guided
+    distribution `lu + cfg_scale * (lc - lu)` the sampler draws from, never materialised.  The teacher receives no gradient.  steps and ar_order mean what
+    they mean in `token_cross_entropy`: rows at or past a sequence's step count are IGNORED (no loss, a zero gradient row, none of their logits read).
+    weights: [S] by TOKENIZER position (row s meets position S - 1 - s when ar_order) or [B, S] by row.  reduction: "mean" (sum of w * kl over sum of w, over
+    the live rows), "sum" or "none" ([B, S], 0 on ignored rows).  The gradient is computed IN THE FORWARD LAUNCH, scaled per row on the device; `loss.backward()`
+    multiplies that buffer by the upstream gradient.  One backward per forward; double backward is refused.  inplace=True writes the gradient OVER
+    `student_logits`: THE LOGITS ARE GONE AFTERWARDS.  A bad row makes "mean" and "sum" NaN and has a zero gradient row.  return_stats=True: -> (loss,
+    DistillStats(kl, ce, h_teacher, lse [B, S] each, bad [1], ignored [1])), device tensors."""
+    o = _ops if ops is None else ops
+    if student_logits.dim() != 3 or teacher_logits.shape != student_logits.shape:
+        raise ValueError(f"need student and teacher logits of one shape [B, S, V], got {tuple(student_logits.shape)} and {tuple(teacher_logits.shape)}")
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"reduction must be one of {REDUCTIONS}, got {reduction!r}")
+    if teacher_uncond is None and float(cfg_scale) != 1.0:
+        raise ValueError("a cfg_scale goes with teacher_uncond")
+    B, S, _ = student_logits.shape
+    live = None
+    positions = (S - 1 - torch.arange(S)) if ar_order else torch.arange(S)
+    if steps is not None:                                           # the scorer's rule for partial sequences, on placeholder ids: target -1 = ignored
+        view, reverse, _ = target_view(torch.zeros((B, S), dtype=torch.int32, device=student_logits.device), S, ar_order, steps)
+        live = (view.flip(1) if reverse else view) >= 0
+    w = None
+    if weights is not None:
+        if tuple(weights.shape) == (S,):
+            w = weights.index_select(0, positions.to(weights.device)).unsqueeze(0)
+        elif tuple(weights.shape) == (B, S):
+            w = weights
+        else:
+            raise ValueError(f"weights must be [S] = [{S}] by tokenizer position or [B, S] = [{B}, {S}] by row, got {tuple(weights.shape)}")
+        w = w.detach()
+    unc = None if teacher_uncond is None else teacher_uncond.detach()
+    loss, kl, ce, h, lse, bad, ignored = _TokenDistill.apply(student_logits, teacher_logits.detach(), unc, float(cfg_scale), live, w, C, int(offset), reduction,
+                                                             bool(inplace), o)
+    return (loss, DistillStats(kl, ce, h, lse, bad, ignored)) if return_stats else loss

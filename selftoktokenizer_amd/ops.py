@@ -1933,11 +1933,10 @@ def token_sample(logits: torch.Tensor, ctr: torch.Tensor, ids_out: torch.Tensor,
 # ----------------------------------------------------------------------------------------------
 # token scorer (csrc/token_score.hip): AR logits and KNOWN ids -> log-probability, rank, first code, entropy per row
 # ----------------------------------------------------------------------------------------------
-def _token_rows(what: str, logits: torch.Tensor, ids: torch.Tensor, C, offset, rows_per_seq, reverse_steps):
-    """the row layout one scorer / loss call hands to its kernel: `logits` [R, V] or [B, S, V] flattened to rows without a copy, the window, and the targets'
-    addressing taken from the strides of `ids` -> (rows_shape, R, V, C, offset, row_stride, S, id_seq_stride, id_step_stride, ids_ptr)"""
+def _logit_rows(what: str, logits: torch.Tensor, C, offset, name: str = "logits"):
+    """the row layout of one tensor of logits, [R, V] or [B, S, V] flattened to rows without a copy, and its window -> (rows_shape, R, V, C, offset, row_stride)"""
     if logits.dtype not in _SAMPLE_DTYPES or logits.dim() not in (2, 3):
-        raise _lib.SelftokHipError(f"{what}: `logits` must be fp32 or bf16 [R, V] or [B, S, V], got {logits.dtype} {tuple(logits.shape)}")
+        raise _lib.SelftokHipError(f"{what}: `{name}` must be fp32 or bf16 [R, V] or [B, S, V], got {logits.dtype} {tuple(logits.shape)}")
     V = logits.shape[-1]
     rows_shape = tuple(logits.shape[:-1])
     R = 1
@@ -1951,15 +1950,22 @@ def _token_rows(what: str, logits: torch.Tensor, ids: torch.Tensor, C, offset, r
     if offset < 0 or C < 1 or offset + C > V:
         raise _lib.SelftokHipError(f"{what}: the window [{offset}, {offset} + {C}) does not lie inside a row of {V} codes")
     if V and logits.stride(-1) != 1:
-        raise _lib.SelftokHipError(f"{what}: `logits` rows must have unit element stride, got strides {logits.stride()}")
+        raise _lib.SelftokHipError(f"{what}: `{name}` rows must have unit element stride, got strides {logits.stride()}")
     if logits.dim() == 3 and R > 1 and logits.shape[0] > 1 and logits.shape[1] > 1 and logits.stride(0) != logits.shape[1] * logits.stride(1):
-        raise _lib.SelftokHipError(f"{what}: [B, S, V] `logits` must flatten to rows without a copy (stride(0) == S * stride(1)), got strides {logits.stride()}")
+        raise _lib.SelftokHipError(f"{what}: [B, S, V] `{name}` must flatten to rows without a copy (stride(0) == S * stride(1)), got strides {logits.stride()}")
     if logits.dim() == 2 or logits.shape[1] > 1:
         rs = logits.stride(-2)
     else:
         rs = logits.stride(0)
     if R <= 1:
         rs = max(V, rs)
+    return rows_shape, R, V, C, offset, rs
+
+
+def _token_rows(what: str, logits: torch.Tensor, ids: torch.Tensor, C, offset, rows_per_seq, reverse_steps):
+    """the row layout one scorer / loss call hands to its kernel: `logits` [R, V] or [B, S, V] flattened to rows without a copy, the window, and the targets'
+    addressing taken from the strides of `ids` -> (rows_shape, R, V, C, offset, row_stride, S, id_seq_stride, id_step_stride, ids_ptr)"""
+    rows_shape, R, V, C, offset, rs = _logit_rows(what, logits, C, offset)
     if ids.dtype not in (torch.int32, torch.int64) or ids.dim() not in (1, 2) or ids.numel() != R or (logits.dim() == 3 and ids.dim() == 2 and tuple(ids.shape) != rows_shape):
         raise _lib.SelftokHipError(f"{what}: `ids` must be int32 or int64, [R] or [B, S] with one id per row of `logits` ({R}), got {ids.dtype} {tuple(ids.shape)}")
     if ids.dim() == 2:
@@ -2068,3 +2074,79 @@ def token_xent(logits: torch.Tensor, ids: torch.Tensor, *, C: Optional[int] = No
         _lib.check(_lib.load().selftok_xent_rows(_p(logits), _SAMPLE_DTYPES[logits.dtype], R, C, rs, offset, ids_ptr, ids.element_size(), S, seq_stride, step_stride, V,
                                                  _p(row_scale), z_coef, _p(nll), _p(lse), _p(grad), gs, _p(bad), _p(ignored), _stream()), "selftok_xent_rows")
     return nll, lse, grad, bad, ignored
+
+
+# ----------------------------------------------------------------------------------------------
+# token distillation (csrc/token_distill.hip): student and teacher logits -> KL, soft cross-entropy, teacher entropy, student lse and the gradient row
+# ----------------------------------------------------------------------------------------------
+def _row_stride_of(t: torch.Tensor, R: int, V: int) -> int:
+    rs = t.stride(-2) if (t.dim() == 2 or t.shape[1] > 1) else t.stride(0)
+    return max(V, rs) if R <= 1 else rs
+
+
+def token_distill(student: torch.Tensor, teacher: torch.Tensor, *, teacher_uncond: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, C: Optional[int] = None,
+                  offset: int = 0, row_scale: Optional[torch.Tensor] = None, row_mask: Optional[torch.Tensor] = None, grad: Optional[torch.Tensor] = None,
+                  inplace: bool = False, want_grad: bool = True, kl: Optional[torch.Tensor] = None, ce: Optional[torch.Tensor] = None,
+                  h_teacher: Optional[torch.Tensor] = None, lse_student: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None,
+                  ignored: Optional[torch.Tensor] = None):
+    """KL(teacher || student) per row and its gradient in one launch: `student` exactly as `token_xent` takes its logits ([R, V] or [B, S, V], fp32 or bf16,
+    window [offset, offset + C)), `teacher` of the same SHAPE with its own dtype (fp32 or bf16) and its own row stride, at temperature 1 on both sides --
+    include/selftok_hip_ext.h states the arithmetic.  `teacher_uncond` (the teacher's shape, dtype and strides) makes the teacher the guided distribution of
+    the sampler, `lu + cfg_scale * (lc - lu)` with lc = `teacher`.  Row r gets kl, ce = -sum pA log pB, h_teacher = -sum pA log pA, lse_student, and the
+    gradient row g * (softmax(student) - softmax(teacher)), g = row_scale[r] (fp32, one per row; None: 1), over all V columns: zero outside the window.
+    `row_mask`: uint8 or bool, one per row; a 0 makes the row IGNORED (nothing of it is read, outputs +0, a zero gradient row).  `grad` / inplace=True as in
+    `token_xent` (in place the gradient lands over `student`); want_grad=False writes no gradient at all and returns None for it (metrics only).  A BAD row
+    (NaN / +inf in either window or in the guided teacher, or a window with nothing above -inf) has NaN outputs and a zero gradient row; a row whose student
+    lies 32768 or more (or at -inf) below its maximum on a code the teacher gives mass has ce = kl = +inf and is not bad.
+    -> (kl, ce, h_teacher, lse_student fp32 shaped [R] or [B, S], grad or None, bad 32-bit [1], ignored 32-bit [1]); bad and ignored ACCUMULATE.  No
+    synchronisation, nothing read back."""
+    what = "token_distill"
+    rows_shape, R, V, C, offset, rs = _logit_rows(what, student, C, offset, "student")
+    if teacher.dtype not in _SAMPLE_DTYPES or teacher.shape != student.shape:
+        raise _lib.SelftokHipError(f"{what}: `teacher` must be fp32 or bf16 of the student's shape {tuple(student.shape)}, got {teacher.dtype} {tuple(teacher.shape)}")
+    ts = _logit_rows(what, teacher, C, offset, "teacher")[5]
+    if teacher_uncond is not None:
+        if teacher_uncond.dtype != teacher.dtype or teacher_uncond.shape != teacher.shape or (R > 1 and teacher_uncond.stride() != teacher.stride()) or \
+                (V and teacher_uncond.stride(-1) != 1):
+            raise _lib.SelftokHipError(f"{what}: `teacher_uncond` must have the dtype, shape and strides of `teacher` ({teacher.dtype} {tuple(teacher.shape)}), got "
+                                       f"{teacher_uncond.dtype} {tuple(teacher_uncond.shape)}")
+        cfg_scale = float(cfg_scale)
+        if cfg_scale != cfg_scale or cfg_scale in (float("inf"), -float("inf")):
+            raise _lib.SelftokHipError(f"{what}: need a finite cfg_scale, got {cfg_scale}")
+    _need_cuda(student, teacher, teacher_uncond, row_scale, row_mask, grad, kl, ce, h_teacher, lse_student, bad, ignored)
+    gs = 0
+    if not want_grad:
+        if inplace or grad is not None:
+            raise _lib.SelftokHipError(f"{what}: want_grad=False writes no gradient: pass neither `grad` nor inplace=True")
+    elif inplace:
+        if grad is not None and grad is not student:
+            raise _lib.SelftokHipError(f"{what}: inplace=True writes the gradient over `student`: pass no `grad`")
+        grad, gs = student, rs
+    else:
+        if grad is None:
+            grad = torch.empty(tuple(student.shape), dtype=student.dtype, device=student.device)
+        if grad.dtype != student.dtype or grad.shape != student.shape or (V and grad.stride(-1) != 1) or \
+                (grad.dim() == 3 and R > 1 and grad.shape[0] > 1 and grad.shape[1] > 1 and grad.stride(0) != grad.shape[1] * grad.stride(1)):
+            raise _lib.SelftokHipError(f"{what}: `grad` must have the dtype and shape of `student`, unit code stride and rows that flatten without a copy, got "
+                                       f"{grad.dtype} {tuple(grad.shape)} strides {grad.stride()}")
+        gs = _row_stride_of(grad, R, V)
+    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.numel() != R or not row_scale.is_contiguous()):
+        raise _lib.SelftokHipError(f"{what}: `row_scale` must be a contiguous fp32 tensor with one element per row ({R}), got {row_scale.dtype} {tuple(row_scale.shape)}")
+    if row_mask is not None and (row_mask.dtype not in (torch.uint8, torch.bool) or row_mask.numel() != R or not row_mask.is_contiguous()):
+        raise _lib.SelftokHipError(f"{what}: `row_mask` must be a contiguous uint8 or bool tensor with one element per row ({R}), got {row_mask.dtype} {tuple(row_mask.shape)}")
+    dev = student.device
+    kl = _out(what, kl, torch.float32, rows_shape, dev, "kl")
+    ce = _out(what, ce, torch.float32, rows_shape, dev, "ce")
+    h_teacher = _out(what, h_teacher, torch.float32, rows_shape, dev, "h_teacher")
+    lse_student = _out(what, lse_student, torch.float32, rows_shape, dev, "lse_student")
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if ignored is None:
+        ignored = torch.zeros(1, dtype=torch.int32, device=dev)
+    _token_u32(what, "bad", bad, (1,))
+    _token_u32(what, "ignored", ignored, (1,))
+    if R:
+        _lib.check(_lib.load().selftok_distill_rows(_p(student), _SAMPLE_DTYPES[student.dtype], _p(teacher), _p(teacher_uncond), _SAMPLE_DTYPES[teacher.dtype], R, C, rs,
+                                                    ts, offset, float(cfg_scale), V, _p(row_scale), _p(row_mask), _p(kl), _p(ce), _p(h_teacher), _p(lse_student),
+                                                    _p(grad), gs, _p(bad), _p(ignored), _stream()), "selftok_distill_rows")
+    return kl, ce, h_teacher, lse_student, grad, bad, ignored

@@ -19,6 +19,7 @@ rank and entropy of every known id under the same arithmetic, and NLL / perplexi
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -220,3 +221,54 @@ def score_tokens(logits: torch.Tensor, ids: torch.Tensor, *, ar_order: bool = Tr
     out = o.token_score(logits, view, uncond_logits=uncond_logits, C=C, offset=offset, cfg_scale=1.0 if cfg_scale is None else float(cfg_scale),
                         temperature=float(temperature), reverse_steps=reverse)
     return TokenScore(*out, positions=positions, K=K)
+
+
+# ---- how far apart are two next-token distributions? (csrc/token_distill.hip without its gradient, `ops.token_distill(want_grad=False)`) ----
+class TokenKL(namedtuple("TokenKL", "kl ce entropy_p bad ignored")):
+    """The device tensors of one `token_kl` call: kl = KL(p || q), ce = -sum p log q and entropy_p = -sum p log p, fp32 [B, S] each, and the two counters.
+    `live` ([B, S] bool or None) and `positions` ([S]: the tokenizer position column s stands for) ride along as attributes.  The reductions are torch fp64
+    on the device; they leave out ignored rows and REFUSE to summarise while bad > 0 (one read-back) unless allow_bad=True, which leaves bad rows out too."""
+
+    def _ok(self, allow_bad: bool) -> torch.Tensor:
+        n_bad = int(self.bad.reshape(-1)[0])
+        if n_bad > 0 and not allow_bad:
+            raise ValueError(f"{n_bad} bad rows (NaN / +inf / all -inf logits): pass allow_bad=True to summarise the rest")
+        ok = ~torch.isnan(self.kl)
+        return ok if self.live is None else ok & self.live
+
+    def mean(self, field: str = "kl", allow_bad: bool = False) -> torch.Tensor:
+        """the mean of `field` over the live rows, 0-d fp64"""
+        ok = self._ok(allow_bad)
+        return torch.where(ok, getattr(self, field).double(), torch.zeros((), dtype=torch.float64, device=self.kl.device)).sum() / ok.sum().double()
+
+    def per_position(self, field: str = "kl", allow_bad: bool = False) -> torch.Tensor:
+        """[S] fp64, indexed by TOKENIZER position; NaN where no row was live"""
+        ok = self._ok(allow_bad)
+        col = torch.where(ok, getattr(self, field).double(), torch.zeros((), dtype=torch.float64, device=self.kl.device)).sum(dim=0) / ok.sum(dim=0).double()
+        out = torch.full((len(self.positions),), float("nan"), dtype=torch.float64, device=col.device)
+        out[torch.from_numpy(np.asarray(self.positions, dtype=np.int64)).to(col.device)] = col
+        return out
+
+
+def token_kl(logits_p: torch.Tensor, logits_q: torch.Tensor, *, uncond_p: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, ar_order: bool = True, steps=None,
+             C: Optional[int] = None, offset: int = 0, ops=None) -> TokenKL:
+    """KL(p || q) per row between two next-token distributions given as logits [B, S, V] (fp32 or bf16 each, on their own), over the window
+    [offset, offset + C): how far guidance (`uncond_p` with `cfg_scale`: p is the guided `lu + s (lc - lu)`), a fine-tune or a quantised model moves the
+    distribution.  ar_order and steps as in `score_tokens`: rows at or past a sequence's step count are ignored.  No gradient is written and nothing is read
+    back."""
+    o = _ops if ops is None else ops
+    if logits_p.dim() != 3 or logits_q.shape != logits_p.shape:
+        raise ValueError(f"need two logits tensors of one shape [B, S, V], got {tuple(logits_p.shape)} and {tuple(logits_q.shape)}")
+    if uncond_p is None and float(cfg_scale) != 1.0:
+        raise ValueError("a cfg_scale goes with uncond_p")
+    B, S, _ = logits_p.shape
+    positions = (S - 1 - np.arange(S)) if ar_order else np.arange(S)
+    live = None
+    if steps is not None:
+        view, reverse, _ = target_view(torch.zeros((B, S), dtype=torch.int32, device=logits_p.device), S, ar_order, steps)
+        live = (view.flip(1) if reverse else view) >= 0
+    kl, ce, h, _, _, bad, ignored = o.token_distill(logits_q, logits_p, teacher_uncond=uncond_p, cfg_scale=float(cfg_scale), C=C, offset=offset,
+                                                    row_mask=None if live is None else live.to(torch.uint8).contiguous(), want_grad=False)
+    out = TokenKL(kl, ce, h, bad, ignored)
+    out.live, out.positions = live, positions
+    return out
