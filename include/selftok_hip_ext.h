@@ -551,6 +551,62 @@ int selftok_distill_rows(const void* student, int dtype, const void* teacher, co
                          long teacher_stride, long offset, float cfg_scale, long V, const float* row_scale, const unsigned char* row_mask, float* kl, float* ce,
                          float* h_teacher, float* lse_student, void* grad, long grad_stride, unsigned* bad, unsigned* ignored, hipStream_t stream);
 
+/* ---- speculative token sampling: S drafted ids per sequence verified against the TARGET model's logits, the accepted prefix committed
+ *      (csrc/token_verify.hip) ----
+ * The accept / reject rule of speculative sampling on the sampler's integer arithmetic: masses are integers, sums are integer sums, both filters are
+ * prefixes of one total order and every draw is counter-based, so the whole round is restated in numpy with Python integers
+ * (tests/token_spec_cases.py) and, with draft logits equal to target logits, the emitted ids are bit for bit those of selftok_sample_token stepped
+ * alone.  Two launches (verify, commit), capturable, no workspace, no synchronisation; every refusal is decided on the host before the first launch
+ * (SELFTOK_EINVAL with a message) and leaves every buffer untouched.  A row's outputs depend on that row's inputs alone.
+ *
+ * Rows.  Row r = b * (S + 1) + s, sequence b in [0, B), slot s in [0, S]; 0 <= S <= 64.  The target row (b, s) holds its window at elements
+ *   b * target_seq_stride + s * target_row_stride + offset .. + C - 1 of `target` (and of target_uncond, the same layout, or null); the draft row
+ *   (b, s), s < S, likewise in `draft` / draft_uncond with the draft's strides.  Each side has its own dtype (0 = fp32, 1 = bf16), its own optional
+ *   unconditional rows and its own scale (cfg_scale, draft_cfg_scale); temperature, top_k, top_p, the seed, C and offset are shared.  1 <= C <= 65536,
+ *   offset + C <= either row stride; every logits pointer is aligned to four codes of its dtype, offset and every row and sequence stride are
+ *   multiples of 4.  The drafted id x of row (b, s) is the int32 / int64 (draft_id_bytes 4 / 8) at element b * draft_id_stride + s of draft_ids, read
+ *   only for s < n_draft[b]; a row with s >= n_draft[b], and a row whose id is negative, HAS NO DRAFT (x = -1): the bonus row s = n_draft[b] and any
+ *   row past it.  n_draft: null (every sequence drafted S ids), or B counts given TWICE -- n_draft_host, host memory, checked here against
+ *   0 <= n_draft[b] <= S, and n_draft, its device copy, which the kernels read (and clamp to [0, S]).  ctr: uint32 [B, 2], (ticket, step) of the
+ *   sampler; row (b, s) uses the counter (ticket_b, step_b + s).
+ * Both distributions.  Steps 1 - 6 of the sampler's text hold word for word for either row: guidance in separate roundings and l * inv_T, the bad-row
+ *   rule, the total order, the integer mass relative to the row's OWN maximum, the top-k prefix, the top-p prefix.  p_i is the target mass of code i
+ *   if i lies inside the target's kept set, else 0; P = sum p_i is the target's Q_kept.  d_i and D likewise for the draft.  Every mass is <= 2^32,
+ *   every total < 2^49.  GREEDY (temperature 0): each kept set is the first code of its order, with mass 2^32; the rules below then say: accept iff x
+ *   is the first code of both sides; the replacement is the target's first code.
+ * Accept test (a row with a draft).  u32 = word 0 of Philox4x32-10(counter (ticket, step, 1, 0), key (seed_lo, seed_hi)).
+ *   accept iff d_x > 0 and u32 * d_x * P < p_x * D * 2^32, both sides exact integers below 2^114 (128-bit products built from 64-bit multiplies and
+ *   their high halves; no division, no floating point).  The acceptance probability is therefore min(1, p_x D / (d_x P)) ROUNDED UP to a multiple
+ *   of 2^-32: ceil(2^32 p_x D / (d_x P)) of the 2^32 values of u32 accept (all of them once the ratio reaches 1).
+ *   d_x == 0 is a FOREIGN draft id -- not drawn from this draft distribution: rejected, foreign[0] += 1; it is not a bad row.
+ * Replacement (a rejected row with a draft).  w_i = (p_i * D - d_i * P) >> 34 where the 128-bit difference is positive, else 0.  p_i * D < 2^82, so
+ *   w_i < 2^48; sum w_i <= sum p_i * D / 2^34 = P * D / 2^34 < 2^98 / 2^34 = 2^64: a uint64 sum never wraps.  Resolution: a residual below 2^34
+ *   of the P * D scale -- a residual probability below 2^34 / (P D) <= 2^-30 (P, D >= 2^32) -- is dropped.  u64 = out[0] | out[1] << 32 of
+ *   Philox(counter (ticket, step, 2, 0)); need = mulhi64(u64, sum w) + 1; the replacement is the first code IN ASCENDING INDEX whose running weight
+ *   reaches need (the sampler's step 7 on the weights w).  sum w == 0 (x foreign while p and d are one distribution; never after an honest
+ *   rejection): the row falls back to the draw below.
+ * A row without a draft is the sampler's step 7 on p with the counter (ticket, step, 0, 0): the id, n_kept, Q_kept, the id's mass and the logprob of
+ *   selftok_sample_token on that row, bit for bit.
+ * BAD rows: a NaN or +inf in either side's l, nothing above -inf on either side (the draft's side only when the row has a draft), or x >= C:
+ *   accept 0, repl_id -1, n_kept 0, the four masses 0, both logprobs NaN, bad[0] += 1.
+ * Per-row outputs, dense [B * (S + 1)]: accept uint8; repl_id int32 (the replacement or the no-draft draw; -1 on an accepted and on a bad row);
+ *   n_kept int32, the target's; mass uint64 [., 4] = (P, D, p_x, d_x) -- a row without a draft: (P, 0, the mass of the drawn code, 0); logprob_x
+ *   and logprob_repl fp32: ((double) l_id - (double) m) - log((double) Q_total * 2^-32) of the TARGET row for x and for repl_id, the sampler's
+ *   formula (NaN where there is no such id).  foreign and bad count over ALL B * (S + 1) rows and accumulate: the caller zeroes them.  Rows past
+ *   the first rejection are computed and then discarded: every row is its own workgroup and none can know the prefix.
+ * Commit, per sequence: n_accept[b] = the first s < n_draft[b] with accept 0, or n_draft[b]; n_emit[b] = max(0, min(n_accept[b] + 1, K - step_b)).
+ *   For j < n_emit[b], tokenizer position K - 1 - (step_b + j) of row b of ids (int32 / int64, id_bytes), logprob_out and n_kept_out (row strides in
+ *   elements, each >= K) receives: the drafted id, logprob_x and n_kept of row (b, j) for j < n_accept[b]; repl_id, logprob_repl and n_kept of row
+ *   (b, n_accept[b]) for j == n_accept[b] (a bad row there commits id -1, NaN, 0, as the sampler does).  Then ctr[b][1] += n_emit[b].
+ * B == 0 returns 0 without a launch. */
+int selftok_verify_draft(const void* target, const void* target_uncond, int target_dtype, long target_seq_stride, long target_row_stride, const void* draft,
+                         const void* draft_uncond, int draft_dtype, long draft_seq_stride, long draft_row_stride, const void* draft_ids, int draft_id_bytes,
+                         long draft_id_stride, const int* n_draft_host, const int* n_draft, int B, int S, int C, long offset, float cfg_scale,
+                         float draft_cfg_scale, float temperature, int top_k, float top_p, unsigned seed_lo, unsigned seed_hi, unsigned* ctr,
+                         unsigned char* accept, int* repl_id, int* n_kept, unsigned long long* mass, float* logprob_x, float* logprob_repl, void* ids,
+                         int id_bytes, long id_row_stride, int K, float* logprob_out, long logprob_row_stride, int* n_kept_out, long n_kept_row_stride,
+                         int* n_accept, int* n_emit, unsigned* foreign, unsigned* bad, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

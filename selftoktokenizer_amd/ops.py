@@ -5,9 +5,11 @@ libselftok_hip.so, and returns torch tensors.  PyTorch is only the allocator / s
 """
 from __future__ import annotations
 
+import collections
 import functools
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1928,6 +1930,115 @@ def token_sample(logits: torch.Tensor, ctr: torch.Tensor, ids_out: torch.Tensor,
                                                 ids_out.stride(0) if B > 1 else K, K if pos is not None else 1, _p(n_kept), _p(mass), _p(logprob), _p(bad), _stream()),
                "selftok_sample_token")
     return n_kept, mass, logprob, bad
+
+
+# ----------------------------------------------------------------------------------------------
+# speculative sampling (csrc/token_verify.hip): S drafted ids per sequence verified against the target's logits, the accepted prefix committed
+# ----------------------------------------------------------------------------------------------
+VerifyOut = collections.namedtuple("VerifyOut", "accept repl_id n_kept mass logprob_x logprob_repl n_accept n_emit foreign bad")
+
+
+def _spec_rows(what: str, name: str, t: torch.Tensor, B: int, rows: int):
+    """[B, rows, V] logits -> (V, sequence stride, row stride) in elements; a dimension of one element gets the stride a dense tensor would have"""
+    if t.dtype not in _SAMPLE_DTYPES or t.dim() != 3 or t.shape[0] != B or t.shape[1] != rows:
+        raise _lib.SelftokHipError(f"{what}: `{name}` must be fp32 or bf16 [{B}, {rows}, V], got {t.dtype} {tuple(t.shape)}")
+    V = int(t.shape[2])
+    if V and t.stride(2) != 1:
+        raise _lib.SelftokHipError(f"{what}: `{name}` rows must have unit element stride, got strides {t.stride()}")
+    row = int(t.stride(1)) if rows > 1 else V + (-V) % 4
+    seq = int(t.stride(0)) if B > 1 else max(rows * row, 0)
+    return V, seq, row
+
+
+def token_verify(target_logits: torch.Tensor, draft_logits: Optional[torch.Tensor], draft_ids: Optional[torch.Tensor], ctr: torch.Tensor, ids: torch.Tensor,
+                 logprob: torch.Tensor, n_kept: torch.Tensor, *, target_uncond: Optional[torch.Tensor] = None, draft_uncond: Optional[torch.Tensor] = None,
+                 C: Optional[int] = None, offset: int = 0, cfg_scale: float = 1.0, draft_cfg_scale: float = 1.0, temperature: float = 1.0, top_k: int = 0,
+                 top_p: float = 1.0, seed: int = 0, n_draft=None, n_draft_dev: Optional[torch.Tensor] = None, accept: Optional[torch.Tensor] = None,
+                 repl_id: Optional[torch.Tensor] = None, row_n_kept: Optional[torch.Tensor] = None, mass: Optional[torch.Tensor] = None,
+                 logprob_x: Optional[torch.Tensor] = None, logprob_repl: Optional[torch.Tensor] = None, n_accept: Optional[torch.Tensor] = None,
+                 n_emit: Optional[torch.Tensor] = None, foreign: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None) -> VerifyOut:
+    """One round of speculative sampling: `target_logits` [B, S + 1, V] and `draft_logits` [B, S, V] (fp32 or bf16 each, on their own; None when S = 0) over
+    the window [offset, offset + C), `draft_ids` [B, S] (int32 / int64, AR order, 0-based inside the window, unit column stride) -- include/selftok_hip_ext.h
+    states the arithmetic.  Each side takes its own unconditional logits (the shape, dtype and strides of its conditional ones) and scale.  `ctr` [B, 2] is
+    the sampler's (ticket, step); row (b, s) uses the counter (ticket, step + s).  `n_draft`: None (every sequence drafted S ids) or B HOST integers in
+    [0, S] (checked on the host; copied to the device here without a synchronisation, or pass the copy yourself as `n_draft_dev` int32 [B]).
+    The verdicts are committed into the sampler's `ids` (int32 / int64), `logprob` (fp32) and `n_kept` (int32) [B, K] matrices at tokenizer positions
+    K - 1 - (step + j), and ctr[:, 1] advances by n_emit.  -> VerifyOut: per row [B, S + 1] accept uint8, repl_id int32, n_kept int32, mass int64 [B, S + 1, 4]
+    holding the uint64 (P, D, p_x, d_x), logprob_x and logprob_repl fp32; per sequence n_accept and n_emit int32 [B]; foreign and bad 32-bit [1],
+    accumulating.  Preallocated outputs are taken as given.  No synchronisation, nothing read back."""
+    what = "token_verify"
+    _need_cuda(target_logits, draft_logits, draft_ids, ctr, ids, logprob, n_kept, target_uncond, draft_uncond, n_draft_dev, accept, repl_id, row_n_kept, mass,
+               logprob_x, logprob_repl, n_accept, n_emit, foreign, bad)
+    if target_logits.dim() != 3 or target_logits.shape[1] < 1:
+        raise _lib.SelftokHipError(f"{what}: `target_logits` must be [B, S + 1, V], got {tuple(target_logits.shape)}")
+    B, S = int(target_logits.shape[0]), int(target_logits.shape[1]) - 1
+    V, t_seq, t_row = _spec_rows(what, "target_logits", target_logits, B, S + 1)
+    if C is None:
+        C = V - int(offset)
+    C, offset = int(C), int(offset)
+    if offset < 0 or C < 1 or offset + C > V:
+        raise _lib.SelftokHipError(f"{what}: the window [{offset}, {offset} + {C}) does not lie inside a target row of {V} codes")
+    d_seq = d_row = id_stride = 0
+    if S > 0:
+        if draft_logits is None or draft_ids is None:
+            raise _lib.SelftokHipError(f"{what}: {S + 1} target rows per sequence need draft_logits [B, {S}, V] and draft_ids [B, {S}]")
+        Vd, d_seq, d_row = _spec_rows(what, "draft_logits", draft_logits, B, S)
+        if offset + C > Vd:
+            raise _lib.SelftokHipError(f"{what}: the window [{offset}, {offset} + {C}) does not lie inside a draft row of {Vd} codes")
+        if draft_ids.dtype not in (torch.int32, torch.int64) or tuple(draft_ids.shape) != (B, S) or draft_ids.stride(1) != 1:
+            raise _lib.SelftokHipError(f"{what}: `draft_ids` must be int32 or int64 [{B}, {S}] with unit column stride, got {draft_ids.dtype} {tuple(draft_ids.shape)}")
+        id_stride = int(draft_ids.stride(0)) if B > 1 else S
+    else:
+        draft_logits = draft_ids = draft_uncond = None
+    for un, lg, name in ((target_uncond, target_logits, "target_uncond"), (draft_uncond, draft_logits, "draft_uncond")):
+        if un is not None and (un.dtype != lg.dtype or un.shape != lg.shape or                      # the stride of a dimension of one element addresses nothing
+                               any(n > 1 and a != b for n, a, b in zip(lg.shape, un.stride(), lg.stride()))):
+            raise _lib.SelftokHipError(f"{what}: `{name}` must have the dtype, shape and strides of its conditional logits")
+    if ctr.dtype not in (torch.int32, torch.uint32) or tuple(ctr.shape) != (B, 2) or not ctr.is_contiguous():
+        raise _lib.SelftokHipError(f"{what}: `ctr` must be a contiguous 32-bit integer tensor [{B}, 2], got {ctr.dtype} {tuple(ctr.shape)}")
+    if ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1 or ids.stride(1) != 1:
+        raise _lib.SelftokHipError(f"{what}: `ids` must be int32 or int64 [{B}, K] with unit column stride, got {ids.dtype} {tuple(ids.shape)}")
+    K = int(ids.shape[1])
+    for t, dt, name in ((logprob, torch.float32, "logprob"), (n_kept, torch.int32, "n_kept")):
+        if t.dtype != dt or tuple(t.shape) != (B, K) or t.stride(1) != 1:
+            raise _lib.SelftokHipError(f"{what}: `{name}` must be {str(dt).replace('torch.', '')} [{B}, {K}] with unit column stride, got {t.dtype} {tuple(t.shape)}")
+    dev = target_logits.device
+    nd_host = None
+    if n_draft is not None:
+        nd_host = np.ascontiguousarray(np.asarray(n_draft, dtype=np.int64).reshape(-1).astype(np.int32))
+        if nd_host.shape != (B,):
+            raise _lib.SelftokHipError(f"{what}: `n_draft` must hold {B} host integers, got {nd_host.shape}")
+        if n_draft_dev is None:
+            n_draft_dev = torch.from_numpy(nd_host).to(dev, non_blocking=True)
+        if n_draft_dev.dtype != torch.int32 or tuple(n_draft_dev.shape) != (B,) or not n_draft_dev.is_contiguous():
+            raise _lib.SelftokHipError(f"{what}: `n_draft_dev` must be a contiguous int32 tensor [{B}]")
+    elif n_draft_dev is not None:
+        raise _lib.SelftokHipError(f"{what}: `n_draft_dev` goes with the host counts `n_draft` it is a copy of")
+    R = (B, S + 1)
+    accept = _out(what, accept, torch.uint8, R, dev, "accept")
+    repl_id = _out(what, repl_id, torch.int32, R, dev, "repl_id")
+    row_n_kept = _out(what, row_n_kept, torch.int32, R, dev, "row_n_kept")
+    mass = _out(what, mass, torch.int64, R + (4,), dev, "mass")
+    logprob_x = _out(what, logprob_x, torch.float32, R, dev, "logprob_x")
+    logprob_repl = _out(what, logprob_repl, torch.float32, R, dev, "logprob_repl")
+    n_accept = _out(what, n_accept, torch.int32, (B,), dev, "n_accept")
+    n_emit = _out(what, n_emit, torch.int32, (B,), dev, "n_emit")
+    if foreign is None:
+        foreign = torch.zeros(1, dtype=torch.int32, device=dev)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    _token_u32(what, "foreign", foreign, (1,))
+    _token_u32(what, "bad", bad, (1,))
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    rs = lambda t: int(t.stride(0)) if B > 1 else K
+    _lib.check(_lib.load().selftok_verify_draft(
+        _p(target_logits), _p(target_uncond), _SAMPLE_DTYPES[target_logits.dtype], t_seq, t_row, _p(draft_logits), _p(draft_uncond),
+        _SAMPLE_DTYPES[draft_logits.dtype] if S > 0 else 0, d_seq, d_row, _p(draft_ids), draft_ids.element_size() if S > 0 else 8, id_stride,
+        None if nd_host is None else nd_host.ctypes.data, _p(n_draft_dev), B, S, C, offset, float(cfg_scale), float(draft_cfg_scale), float(temperature), int(top_k),
+        float(top_p), seed & 0xFFFFFFFF, seed >> 32, _p(ctr), _p(accept), _p(repl_id), _p(row_n_kept), _p(mass), _p(logprob_x), _p(logprob_repl), _p(ids),
+        ids.element_size(), rs(ids), K, _p(logprob), rs(logprob), _p(n_kept), rs(n_kept), _p(n_accept), _p(n_emit), _p(foreign), _p(bad), _stream()),
+        "selftok_verify_draft")
+    return VerifyOut(accept, repl_id, row_n_kept, mass, logprob_x, logprob_repl, n_accept, n_emit, foreign, bad)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -16,6 +16,10 @@ and that sample's logits alone: the same request gives the same ids alone or in 
 
 The teacher-forced side (csrc/token_score.hip, `ops.token_score`): `score_tokens(logits[B, S, V], ids[B, K])` gives a `TokenScore` -- the log-probability,
 rank and entropy of every known id under the same arithmetic, and NLL / perplexity / top-k accuracy / per-position NLL over them.
+
+Speculative sampling (csrc/token_verify.hip, `ops.token_verify`): a small model drafts S tokens through a `fork()` of the sampler, the large model scores
+S + 1 positions in one forward, `verify()` keeps a prefix of the draft and replaces the first rejected token -- distributed as if the large model had
+sampled alone, and with draft logits equal to target logits bit for bit the ids of the plain `step` loop.
 """
 from __future__ import annotations
 
@@ -26,6 +30,11 @@ import numpy as np
 import torch
 
 from . import ops as _ops
+
+
+SpecRound = namedtuple("SpecRound", "n_accept n_emit foreign bad")
+SpecRound.__doc__ = """One `TokenSampler.verify` round: n_accept int32 [B] on the device (drafted tokens kept per sequence), n_emit a HOST int64 array [B] (tokens
+committed per sequence: the kept drafts plus the replacement or bonus token, capped at K), foreign and bad the sampler's accumulating device counters."""
 
 
 class TokenSampler:
@@ -60,12 +69,14 @@ class TokenSampler:
             raise ValueError(f"need {B} tickets in [0, 2^32) and {B} steps in [0, K]")
         self.B = B
         self._steps = steps.copy()                                  # host mirror: the device never has to be asked
+        self._ticket_host, self._fork_steps = tickets.copy(), None
         ctr = np.stack([tickets, steps], axis=1).astype(np.uint32).view(np.int32)
         self.ctr = torch.from_numpy(ctr.copy()).to(device)
         self.ids = torch.zeros(B, self.K, dtype=self.id_dtype, device=device)
         self.logprob = torch.full((B, self.K), float("nan"), dtype=torch.float32, device=device)
         self.n_kept = torch.zeros(B, self.K, dtype=torch.int32, device=device)
         self.bad = torch.zeros(1, dtype=torch.int32, device=device)
+        self.foreign = torch.zeros(1, dtype=torch.int32, device=device)   # drafted ids the draft distribution could not have drawn (verify)
         self._row_lp = torch.empty(B, dtype=torch.float32, device=device)
         self._row_nk = torch.empty(B, dtype=torch.int32, device=device)
         self._row_mass = torch.empty(B, 3, dtype=torch.int64, device=device)
@@ -107,6 +118,63 @@ class TokenSampler:
         if self.B is None:
             raise RuntimeError("TokenSampler.partial before begin")
         return self.ids, (int(self._steps[0]) if self.B and self._uniform() else self._steps.copy())
+
+    # ---- speculative sampling: draft through a fork, verify here ----
+    def fork(self, cfg_scale="same") -> "TokenSampler":
+        """a DRAFT sampler: the same parameters, seed and tickets, the device counters copied as they stand, its own [B, K] matrices.  The drafter runs
+        ordinary `step` calls on it; `drafted()` then hands over what it drew.  cfg_scale: the draft side's own guidance rule (None: an unguided student,
+        the usual product of distilling the guided distribution); by default this sampler's.  Reads nothing back: the host mirror of the steps is copied
+        from this sampler's."""
+        if self.B is None:
+            raise RuntimeError("TokenSampler.fork before begin")
+        d = TokenSampler(self.K, self.C, self.offset, self.temperature, self.top_k, self.top_p, self.cfg_scale if cfg_scale == "same" else cfg_scale, self.seed,
+                         id_dtype=self.id_dtype, ops=self._ops)
+        d.begin(self.B, tickets=self._ticket_host, steps=self._steps, device=self.ctr.device)
+        d.ctr.copy_(self.ctr)
+        d._fork_steps = self._steps.copy()
+        return d
+
+    def drafted(self):
+        """on a fork: (draft_ids [B, S] in AR order, n_draft host int64 [B]) -- the ids drawn since the fork, S the largest count, -1 past a row's own"""
+        if getattr(self, "_fork_steps", None) is None:
+            raise RuntimeError("TokenSampler.drafted: not a fork")
+        n = self._steps - self._fork_steps
+        S = int(n.max()) if self.B else 0
+        if S == 0:
+            return torch.empty(self.B, 0, dtype=self.id_dtype, device=self.ids.device), n
+        pos = (self.K - 1) - (torch.from_numpy(self._fork_steps).to(self.ids.device, non_blocking=True).unsqueeze(1) + torch.arange(S, device=self.ids.device))
+        live = torch.from_numpy(n).to(self.ids.device, non_blocking=True).unsqueeze(1) > torch.arange(S, device=self.ids.device)
+        x = torch.gather(self.ids, 1, pos.clamp_(0, self.K - 1))
+        return torch.where(live, x, torch.full_like(x, -1)), n
+
+    def _read_back(self, t: torch.Tensor) -> np.ndarray:
+        return t.cpu().numpy()
+
+    def verify(self, draft_ids: torch.Tensor, draft_logits: Optional[torch.Tensor], target_logits: torch.Tensor, *, draft_uncond: Optional[torch.Tensor] = None,
+               target_uncond: Optional[torch.Tensor] = None, draft_cfg_scale: Optional[float] = None, n_draft=None) -> SpecRound:
+        """One round of speculative sampling.  draft_ids [B, S] (AR order: what a `fork()` drew, see `drafted`), draft_logits [B, S, V] the logits they were
+        drawn from, target_logits [B, S + 1, V] this model's logits at the same S positions and one more; S = 0 (draft_logits None) is one plain step.
+        target_uncond goes with this sampler's cfg_scale, draft_uncond with draft_cfg_scale, both or neither on each side.  n_draft: host counts <= S for
+        rows that drafted fewer.  Per sequence the longest accepted prefix, then the replacement of the first rejected token (or, when every draft was
+        kept, one more token from the last target row) are written into ids / logprob / n_kept at their tokenizer positions, and the device counters
+        advance by the number emitted, which stops at K.
+
+        THE ONE READ-BACK: after the two launches `n_emit` (B int32 values) is copied to the host, once, the only device -> host copy of a round; the
+        caller needs these counts anyway to crop its KV caches.  It refreshes the host mirror of the steps, so `step`, `partial`, `state` and
+        `load_state` keep working afterwards -- rows are then at different steps, which every one of them supports."""
+        if self.B is None:
+            raise RuntimeError("TokenSampler.verify before begin")
+        if (target_uncond is None) != (self.cfg_scale is None):
+            raise ValueError("unconditional target logits go with a cfg_scale: pass both or neither")
+        if (draft_uncond is None) != (draft_cfg_scale is None):
+            raise ValueError("unconditional draft logits go with a draft_cfg_scale: pass both or neither")
+        out = self._ops.token_verify(target_logits, draft_logits, draft_ids, self.ctr, self.ids, self.logprob, self.n_kept, target_uncond=target_uncond,
+                                     draft_uncond=draft_uncond, C=self.C, offset=self.offset, cfg_scale=1.0 if self.cfg_scale is None else self.cfg_scale,
+                                     draft_cfg_scale=1.0 if draft_cfg_scale is None else float(draft_cfg_scale), temperature=self.temperature,
+                                     top_k=self.top_k, top_p=self.top_p, seed=self.seed, n_draft=n_draft, foreign=self.foreign, bad=self.bad)
+        n_emit = self._read_back(out.n_emit).astype(np.int64)
+        self._steps = self._steps + n_emit
+        return SpecRound(out.n_accept, n_emit, self.foreign, self.bad)
 
     # ---- resumable requests ----
     def state(self) -> dict:
