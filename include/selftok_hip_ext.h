@@ -607,6 +607,47 @@ int selftok_verify_draft(const void* target, const void* target_uncond, int targ
                          int id_bytes, long id_row_stride, int K, float* logprob_out, long logprob_row_stride, int* n_kept_out, long n_kept_row_stride,
                          int* n_accept, int* n_emit, unsigned* foreign, unsigned* bad, hipStream_t stream);
 
+/* ---- token policy loss: AR logits over a window of C codes, a SAMPLED id per row, the log-probability it was drawn with and its advantage -> the clipped
+ *      PPO / GRPO surrogate's coefficient, the k3 KL estimate to a reference, the entropy, and the gradient row (csrc/token_policy.hip) ----
+ * The reinforcement-learning side of the loss above, on its arithmetic at temperature 1 without guidance: steps 3 - 4 of the sampler's text hold word for
+ * word for m, d_i = l_i - m (fp32), q_i and Q (their integer sum); Lq = log((double) Q * 2^-32) (tests/token_policy_cases.py restates the rest in numpy).
+ * Stateless and capturable, no workspace, no synchronisation; every refusal is decided on the host before the launch (SELFTOK_EINVAL with a message) and
+ * leaves the outputs untouched.  A row's outputs depend on that row's inputs alone.
+ *
+ * Inputs.  logits, dtype, R, C, row_stride, offset, ids, id_bytes, rows_per_seq, id_seq_stride, id_step_stride, V, row_scale, grad, grad_stride: the loss's
+ *   layout, alignment, window, in-place and refusal rules.  grad == NULL: metrics only -- nothing of a gradient is written, V and grad_stride are not looked
+ *   at.  old_logprob, advantage: fp32 dense [R], required.  ref_logprob: fp32 dense [R] or null.  clip_lo, clip_hi, kl_coef, ent_coef: finite, >= 0,
+ *   clip_lo < 1; kl_coef != 0 with a null ref_logprob is refused.  entropy: fp32 [R] or NULL (not wanted).
+ * Per scored row, A = advantage[r], g = row_scale[r] (1.0f when null):
+ *   lse = (float) ((double) m + Lq): the loss's.  lp = logprob = (float) (((double) l_t - (double) m) - Lq): the scorer's, bit for bit.
+ *   ratio = (float) exp((double) lp - (double) old_logprob[r]): the difference is taken from the ROUNDED fp32 lp, so a roll-out scored by selftok_score_tokens
+ *     or selftok_sample_token (temperature 1, unfiltered) gives a difference of exactly 0 and a ratio of exactly 1.0f.
+ *   lo = 1.0f - clip_lo, hi = 1.0f + clip_hi (fp32).  clipped_hi = A > 0 && ratio > hi; clipped_lo = A < 0 && ratio < lo; flags[r] (uint8) = clipped_hi |
+ *     clipped_lo << 1.  The surrogate is clipped_hi ? hi * A : clipped_lo ? lo * A : ratio * A, and +0 for A == 0 whatever the ratio (it is not an output: the
+ *     host forms it from ratio, flags and A).
+ *   kl: with a reference u = (double) ref_logprob[r] - (double) lp, e = expm1(u), kl = (float) (e - u): the k3 estimator exp(u) - u - 1, written so that a
+ *     small u does not cancel.  Without a reference kl = +0 and e = 0.  (u = +inf -- a target at -inf under a finite reference -- gives inf - inf, a NaN kl.)
+ *   entropy, the scorer's, bit for bit: S = sum (uint64) trunc((double) q_i * (double) (-d_i) * 65536.0) over q_i > 0, E = (double) S / (65536.0 * (double) Q),
+ *     H = (float) (Lq + E).  S is formed only when ent_coef != 0 or entropy != NULL.
+ *   coef[r] = k = g * (float) W, W = P + (double) kl_coef * e, P = (clipped_hi || clipped_lo || A == 0) ? 0.0 : (double) A * (double) ratio; each fp64
+ *     operation rounded on its own.  k is minus the derivative of g * (-surrogate + kl_coef * kl) with respect to lp.
+ *   grad, column offset + i: x_i = k * p_i - (i == t ? k : 0), p_i = (float) ((double) q_i * (1.0 / (double) Q)): selftok_xent_rows' formula with a = g = k,
+ *     bit for bit.  With ent_coef != 0 the column gets x_i + kH * t_i instead (fp32 product, fp32 sum), kH = g * ent_coef (fp32), t_i = (float) (((double) q_i *
+ *     (1.0 / (double) Q)) * ((double) d_i + E)) for q_i > 0, else +0: p_i (log p_i + H), the gradient of -H.  With ent_coef == 0 nothing is added (a -0.0
+ *     stays -0.0).  bf16 output is rounded to nearest even once.  Columns [0, offset) and [offset + C, V) are written +0; [V, grad_stride) is never touched.
+ * Row kinds.  IGNORED: a target < 0 on a row the loss would not call bad; its old_logprob, advantage and ref_logprob are not looked at: logprob, ratio, kl,
+ *   entropy and coef +0, lse as for any row, flags 0, a gradient row of zeros WRITTEN, ignored[0] += 1.
+ *   BAD: the loss's conditions (a NaN or +inf logit in the window, nothing above -inf, a target >= C); or, on a row with a target >= 0, a NaN or infinite
+ *   advantage, a NaN or +inf old_logprob or ref_logprob, or a NaN difference (lp = -inf against an old_logprob or ref_logprob of -inf): every fp32 output
+ *   NaN, flags 0, bad[0] += 1, a gradient row of zeros WRITTEN.  A target at -inf with a finite old_logprob is not bad: its ratio is 0.
+ *   bad and ignored accumulate: the caller zeroes them.
+ * In place.  grad == logits with grad_stride == row_stride is allowed and gives the out-of-place bits; any other intersection is refused.
+ * R == 0 returns 0 without a launch. */
+int selftok_policy_rows(const void* logits, int dtype, int R, int C, long row_stride, long offset, const void* ids, int id_bytes, int rows_per_seq,
+                        long id_seq_stride, long id_step_stride, long V, const float* row_scale, const float* old_logprob, const float* advantage,
+                        const float* ref_logprob, float clip_lo, float clip_hi, float kl_coef, float ent_coef, float* logprob, float* lse, float* ratio, float* kl,
+                        float* entropy, float* coef, unsigned char* flags, void* grad, long grad_stride, unsigned* bad, unsigned* ignored, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,8 @@ EXT_SIGNATURES = {
     "selftok_sample_token": (_i, [_vp, _vp, _i, _i, _i, _l, _l, _f, _f, _i, _f, C.c_uint, C.c_uint, _vp, _vp, _vp, _i, _l, _i, _vp, _vp, _vp, _vp, _vp]),
     "selftok_score_tokens": (_i, [_vp, _vp, _i, _i, _i, _l, _l, _f, _f, _vp, _i, _i, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "selftok_xent_rows": (_i, [_vp, _i, _i, _i, _l, _l, _vp, _i, _i, _l, _l, _l, _vp, _f, _vp, _vp, _vp, _l, _vp, _vp, _vp]),
+    "selftok_policy_rows": (_i, [_vp, _i, _i, _i, _l, _l, _vp, _i, _i, _l, _l, _l, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp,
+                                 _vp, _vp]),
     "selftok_distill_rows": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _l, _l, _l, _f, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp]),
     "selftok_verify_draft": (_i, [_vp, _vp, _i, _l, _l, _vp, _vp, _i, _l, _l, _vp, _i, _l, _vp, _vp, _i, _i, _i, _l, _f, _f, _f, _i, _f, C.c_uint, C.c_uint] +
                              [_vp] * 8 + [_i, _l, _i, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp]),

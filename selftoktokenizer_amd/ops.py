@@ -2188,6 +2188,95 @@ def token_xent(logits: torch.Tensor, ids: torch.Tensor, *, C: Optional[int] = No
 
 
 # ----------------------------------------------------------------------------------------------
+# token policy loss (csrc/token_policy.hip): AR logits, SAMPLED ids, their roll-out log-probabilities and advantages -> PPO / GRPO surrogate and gradient
+# ----------------------------------------------------------------------------------------------
+PolicyOut = collections.namedtuple("PolicyOut", "logprob lse ratio kl entropy coef flags grad bad ignored")
+
+
+def _policy_row_operand(what: str, name: str, t, R: int):
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != R or not t.is_contiguous()):
+        got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise _lib.SelftokHipError(f"{what}: `{name}` must be a contiguous fp32 tensor with one element per row ({R}), got {got}")
+
+
+def token_policy(logits: torch.Tensor, ids: torch.Tensor, old_logprob: torch.Tensor, advantage: torch.Tensor, *, ref_logprob: Optional[torch.Tensor] = None,
+                 clip=(0.2, 0.2), kl_coef: float = 0.0, ent_coef: float = 0.0, C: Optional[int] = None, offset: int = 0, row_scale: Optional[torch.Tensor] = None,
+                 grad: Optional[torch.Tensor] = None, inplace: bool = False, want_grad: bool = True, reverse_steps: bool = False, rows_per_seq: Optional[int] = None,
+                 want_entropy: Optional[bool] = None, logprob: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None, ratio: Optional[torch.Tensor] = None,
+                 kl: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None, coef: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None,
+                 bad: Optional[torch.Tensor] = None, ignored: Optional[torch.Tensor] = None):
+    """The clipped PPO / GRPO surrogate on SAMPLED ids, the k3 KL estimate to a frozen reference, the entropy and the gradient row of
+    g * (-surrogate + kl_coef * kl - ent_coef * entropy) in one launch: `logits` and `ids` exactly as `token_xent` takes them (shapes, strides, window,
+    `reverse_steps`), at temperature 1 without guidance -- include/selftok_hip_ext.h states the arithmetic.  `old_logprob`, `advantage` and `ref_logprob`
+    (optional): contiguous fp32, one per row IN ROW ORDER.  clip = (lo, hi): the ratio is held to [1 - lo, 1 + hi] on the side the advantage pushes it; a row
+    whose ratio left the range that way is CLIPPED (flags bit 0: above, bit 1: below) and its policy gradient is zero.  kl_coef != 0 needs `ref_logprob`.
+    `row_scale`, `grad`, inplace=True as in `token_xent`; want_grad=False writes no gradient at all and returns None for it (metrics only).  The entropy is
+    computed when ent_coef != 0, when an `entropy` tensor is passed or when want_entropy=True (default: only then; otherwise None is returned for it).
+    An IGNORED row (target < 0) has +0 outputs (but its lse) and a zero gradient row; a BAD row (the loss's kinds, or a NaN / infinite advantage, a NaN / +inf
+    old or reference log-probability, or -inf against -inf) has NaN outputs and a zero gradient row.
+    -> PolicyOut(logprob, lse, ratio, kl, entropy or None, coef -- fp32 -- flags uint8, shaped [R] or [B, S]; grad or None; bad, ignored 32-bit [1],
+    ACCUMULATING).  No synchronisation, nothing read back."""
+    _need_cuda(logits, ids, old_logprob, advantage, ref_logprob, row_scale, grad, logprob, lse, ratio, kl, entropy, coef, flags, bad, ignored)
+    what = "token_policy"
+    rows_shape, R, V, C, offset, rs, S, seq_stride, step_stride, ids_ptr = _token_rows(what, logits, ids, C, offset, rows_per_seq, reverse_steps)
+    try:
+        clip_lo, clip_hi = (float(clip), float(clip)) if isinstance(clip, (int, float)) else (float(clip[0]), float(clip[1]))
+    except (TypeError, IndexError, ValueError):
+        raise _lib.SelftokHipError(f"{what}: `clip` must be a number or a pair (lo, hi), got {clip!r}")
+    kl_coef, ent_coef = float(kl_coef), float(ent_coef)
+    inf = float("inf")
+    if not (0.0 <= clip_lo < 1.0 and 0.0 <= clip_hi < inf):
+        raise _lib.SelftokHipError(f"{what}: need a clip range with 0 <= lo < 1 and a finite hi >= 0, got ({clip_lo}, {clip_hi})")
+    if not (0.0 <= kl_coef < inf and 0.0 <= ent_coef < inf):
+        raise _lib.SelftokHipError(f"{what}: need a finite kl_coef >= 0 and a finite ent_coef >= 0, got {kl_coef} and {ent_coef}")
+    if kl_coef != 0.0 and ref_logprob is None:
+        raise _lib.SelftokHipError(f"{what}: kl_coef != 0 needs `ref_logprob`")
+    gs = 0
+    if not want_grad:
+        if inplace or grad is not None:
+            raise _lib.SelftokHipError(f"{what}: want_grad=False writes no gradient: pass neither `grad` nor inplace=True")
+    elif inplace:
+        if grad is not None and grad is not logits:
+            raise _lib.SelftokHipError(f"{what}: inplace=True writes the gradient over `logits`: pass no `grad`")
+        grad, gs = logits, rs
+    else:
+        if grad is None:
+            grad = torch.empty(tuple(logits.shape), dtype=logits.dtype, device=logits.device)
+        if grad.dtype != logits.dtype or grad.shape != logits.shape or (V and grad.stride(-1) != 1) or \
+                (grad.dim() == 3 and R > 1 and grad.shape[0] > 1 and grad.shape[1] > 1 and grad.stride(0) != grad.shape[1] * grad.stride(1)):
+            raise _lib.SelftokHipError(f"{what}: `grad` must have the dtype and shape of `logits`, unit code stride and rows that flatten without a copy, got "
+                                       f"{grad.dtype} {tuple(grad.shape)} strides {grad.stride()}")
+        gs = grad.stride(-2) if (grad.dim() == 2 or grad.shape[1] > 1) else grad.stride(0)
+        if R <= 1:
+            gs = max(V, gs)
+    for name, t in (("old_logprob", old_logprob), ("advantage", advantage), ("ref_logprob", ref_logprob), ("row_scale", row_scale)):
+        if t is None and name in ("old_logprob", "advantage"):
+            raise _lib.SelftokHipError(f"{what}: `{name}` is required")
+        _policy_row_operand(what, name, t, R)
+    dev = logits.device
+    logprob = _out(what, logprob, torch.float32, rows_shape, dev, "logprob")
+    lse = _out(what, lse, torch.float32, rows_shape, dev, "lse")
+    ratio = _out(what, ratio, torch.float32, rows_shape, dev, "ratio")
+    kl = _out(what, kl, torch.float32, rows_shape, dev, "kl")
+    coef = _out(what, coef, torch.float32, rows_shape, dev, "coef")
+    flags = _out(what, flags, torch.uint8, rows_shape, dev, "flags")
+    if entropy is not None or want_entropy or (want_entropy is None and ent_coef != 0.0):
+        entropy = _out(what, entropy, torch.float32, rows_shape, dev, "entropy")
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if ignored is None:
+        ignored = torch.zeros(1, dtype=torch.int32, device=dev)
+    _token_u32(what, "bad", bad, (1,))
+    _token_u32(what, "ignored", ignored, (1,))
+    if R:
+        _lib.check(_lib.load().selftok_policy_rows(_p(logits), _SAMPLE_DTYPES[logits.dtype], R, C, rs, offset, ids_ptr, ids.element_size(), S, seq_stride, step_stride, V,
+                                                   _p(row_scale), _p(old_logprob), _p(advantage), _p(ref_logprob), clip_lo, clip_hi, kl_coef, ent_coef, _p(logprob),
+                                                   _p(lse), _p(ratio), _p(kl), _p(entropy), _p(coef), _p(flags), _p(grad), gs, _p(bad), _p(ignored), _stream()),
+                   "selftok_policy_rows")
+    return PolicyOut(logprob, lse, ratio, kl, entropy, coef, flags, grad, bad, ignored)
+
+
+# ----------------------------------------------------------------------------------------------
 # token distillation (csrc/token_distill.hip): student and teacher logits -> KL, soft cross-entropy, teacher entropy, student lse and the gradient row
 # ----------------------------------------------------------------------------------------------
 def _row_stride_of(t: torch.Tensor, R: int, V: int) -> int:
